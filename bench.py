@@ -3,15 +3,20 @@
 64x16 output grid, fp64), one process per GPU, batch sharded with no data-path collective.
 
     python bench.py [--gpus N --steps K --warmup W] [--method cubic|linear|...] [--workload cfg3|cfg4|cfg5]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
 
 A "step" = one pass of the hot path (one ivs_surface_batch_f64 call) over the rank's whole resident shard.  Inputs live
 in HBM before the timed region; the call's scratch is a caller-owned workspace (nothing is allocated inside the loop).
-Rank 0 prints ONE JSON line.
-  N = 1 : the 1M batch of the workload; the line also carries `other_configs` (configs 4 and 5, a few steps each),
-          `cpu_baseline` (C/OpenMP port of the oracle) with `cpu_baseline.others` (B1 reference-shaped, B2 vectorised
-          NumPy: SURVEY 8d / BASELINE.md 3) and `pcie` (H2D / D2H of one chunk: the rate a host-buffer caller would see).
+Rank 0 prints ONE JSON line.  A plain run only sets up, warms up, times the K steps and prints the line (its `roofline`
+comes from the HIP events of those same steps).
+  --full : everything else as well.  N = 1: `other_configs` (configs 4 and 5, a few steps each), `cpu_baseline` (C/OpenMP
+          port of the oracle) with `cpu_baseline.others` (B1 reference-shaped, B2 vectorised NumPy: SURVEY 8d /
+          BASELINE.md 3), `parity_check` (surfaces of the timed batch against the oracle), `pcie` (H2D / D2H of one
+          chunk: the rate a host-buffer caller would see) and `roofline.device_copy_GBps`; N > 1: `cpu_baseline`.
+          `--no-cpu-baseline` / `--no-other-configs` narrow it.
+  --dump-outputs DIR : after the timed steps, what the last step computed (rank 0) as DIR/*.npy, see dump_outputs().
   N > 1 : default `--scaling strong` = BASELINE config 3 as written: ONE 1M batch split over the ranks with
           sharding.shard_bounds (config 5: ragged_shard_bounds, equal strike counts); `--scaling weak` gives every rank
           its own `--batch` surfaces.  value = all surfaces of the job / max-over-ranks time.
@@ -118,6 +123,26 @@ def load_traffic(workload, method, kernel, batch):
         return None
 
 
+DUMP_BYTES = 48 << 20       # --dump-outputs: budget of the sampled output surfaces (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, out, status):
+    """--dump-outputs: what a caller of the timed call holds after the last timed step, at a fixed sample of surfaces
+    (the same on every run with the same arguments): surfaces.npy = out[idx] (float64, [n, mT, mK]), status.npy =
+    status[idx] and surfaces_index.npy = idx (both as float64; idx sorted, drawn with synth.BASE_SEED)."""
+    import numpy as np
+    import torch
+    from iv_interpolation_amd import synth
+    B = out.shape[0]
+    n = max(1, min(B, DUMP_BYTES // (out[0].numel() * 8)))
+    idx = np.sort(np.random.default_rng(synth.BASE_SEED).choice(B, n, replace=False))
+    it = torch.from_numpy(idx).to(out.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "surfaces.npy"), out[it].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), status[it].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "surfaces_index.npy"), idx.astype(np.float64))
+
+
 def build_shard(torch, synth, sharding, workload, B_global, rank, world, scaling, nk_override=0):
     """Inputs of this rank in HBM.  strong: rank r owns the contiguous block shard_bounds(B_global, r, world) of ONE global
     batch (ragged: blocks of equal strike count); weak: every rank owns B_global surfaces.  Each rank generates only its
@@ -144,8 +169,9 @@ def build_shard(torch, synth, sharding, workload, B_global, rank, world, scaling
 
 
 def run_workload(torch, engine, synth, sharding, dist, a, workload, method, B_global, steps, warmup, rank, world, backend,
-                 scaling, want_sample=False):
-    """Generate the shard, run W + K steps, return the measurements of this rank (and, on rank 0, of the job)."""
+                 scaling, want_sample=False, dump_dir=None):
+    """Generate the shard, run W + K steps, return the measurements of this rank (and, on rank 0, of the job).
+    `dump_dir`: write the outputs of the last timed step there (dump_outputs) before anything else runs."""
     nK0, nT, mK, mT, ragged, desc = WORKLOADS[workload]
     d, kw, B, total_strikes, (lo, hi), nK = build_shard(torch, synth, sharding, workload, B_global, rank, world, scaling,
                                                         a.nk if workload == a.workload else 0)
@@ -229,6 +255,8 @@ def run_workload(torch, engine, synth, sharding, dist, a, workload, method, B_gl
         dist.all_reduce(ones)                                       # how many ranks the collective really reached
         ranks_seen = int(ones[0]); total = sum(per_rank_B)
     assert int(status.max()) == 0
+    if dump_dir:
+        dump_outputs(dump_dir, out, status)
 
     # Placement (OFF by default since round 3: `value` and `roofline.frac` are measured on the FIRST allocation, what any
     # caller of engine.surface_batch gets).  On this platform the same kernel on the same inputs runs a few per cent faster
@@ -341,6 +369,12 @@ def main():
     ap.add_argument("--force-generic", action="store_true")
     ap.add_argument("--nan-frac", type=float, default=0.0,
                     help="fraction of quotes set to NaN (= missing): every row then has its own knot set (masked second-pass kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: other configs, CPU baselines, "
+                         "oracle parity check, PCIe rates, device copy rate (off: set up, warm up, time the steps, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (a fixed sample of the output surfaces "
+                         "and their status) as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--placement-tries", type=int, default=1,
                     help="N > 1: after the timed region also time the kernel on the fastest of N - 1 further output allocations "
@@ -348,8 +382,8 @@ def main():
     ap.add_argument("--launch", default="eager", choices=["eager", "graph"],
                     help="graph: capture one call into a hipGraph after the warm-up and time its replays (same kernels, no per-launch host cost)")
     ap.add_argument("--spin-ms", type=float, default=100.0, help="untimed launches before the warm-up steps (clock ramp)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the config-4 / config-5 sub-results of the N = 1 line")
-    ap.add_argument("--check", type=int, default=256, help="surfaces compared with the oracle after the timed region")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the config-4 / config-5 sub-results of the N = 1 line")
+    ap.add_argument("--check", type=int, default=256, help="--full: surfaces compared with the oracle after the timed region")
     ap.add_argument("--gather", action="store_true",
                     help="after the timed region, also time the optional all-gather of the output shards (RCCL over xGMI); "
                          "reported separately as 'gather', never part of 'value'")
@@ -369,7 +403,7 @@ def main():
 
     # CPU baselines that fan out over processes run FIRST: nothing in this process has touched the GPU yet
     pool_baselines = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not ragged:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not ragged:
         pool_baselines = cpu_pool_baselines(a.method, nK, nT, mK, mT)
 
     import torch
@@ -394,11 +428,12 @@ def main():
             torch.cuda.synchronize()
 
     m = run_workload(torch, engine, synth, sharding, dist, a, a.workload, a.method, a.batch, a.steps, a.warmup, rank, world,
-                     backend, scaling, want_sample=(rank == 0 and world == 1 and not a.no_cpu_baseline))
+                     backend, scaling, want_sample=(a.full and rank == 0 and world == 1 and not a.no_cpu_baseline),
+                     dump_dir=a.dump_outputs if rank == 0 else None)
 
     others = {}
-    if world == 1 and not a.no_other_configs and a.workload == "cfg3" and not a.nk and not a.force_generic and a.nan_frac == 0:
-        # the driver runs the default line only: carry the other two BASELINE configs along (a few steps each)
+    if a.full and world == 1 and not a.no_other_configs and a.workload == "cfg3" and not a.nk and not a.force_generic and a.nan_frac == 0:
+        # --full: carry the other two BASELINE configs along (a few steps each)
         for wl, st in (("cfg4", 5), ("cfg5", 5)):
             o = run_workload(torch, engine, synth, sharding, None, a, wl, a.method, a.batch, st, 2, 0, 1, backend, "weak")
             others[wl] = {"workload": f"{wl}: {o['desc']}", "value": o["value"], "unit": "surfaces/s", "steps": st, "warmup": 2,
@@ -406,7 +441,7 @@ def main():
                           "roofline": {k: o["roofline"][k] for k in ("achieved", "peak", "frac", "kernel_ms_avg", "algorithmic_bytes_per_launch")}}
 
     copy_gbps = None
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         # context: what a plain device copy reaches on THIS device (read + write stream), same HIP-event timing
         nbytes = 2 << 30
         src = torch.empty(nbytes // 8, dtype=torch.float64, device="cuda").fill_(1.0); dst = torch.empty_like(src)
@@ -449,7 +484,7 @@ def main():
             res["other_configs"] = others
         if m["pcie"]:
             res["pcie"] = m["pcie"]
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             res["cpu_baseline"], res["parity_check"] = cpu_baseline(a.method, m["nK"], m["nT"], m["mK"], m["mT"],
                                                                    budget_s=20.0 if world == 1 else 8.0, sample=m["sample"],
                                                                    ragged=m["ragged"])
