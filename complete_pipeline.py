@@ -26,13 +26,15 @@ from iv_interpolation_amd.frame_store import FrameStore, synthetic_symbol   # no
 
 MINUTE_TABLE = "minute_candles"
 CANDLE_TABLE = "reconstructed_candles"
+SURFACE_TABLE = "iv_surfaces"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
 class CompleteOptimizedPipeline:
     def __init__(self, config, data_dir: Optional[str] = None, backend=None, bridge_backend=None, candle_backend=None,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, surface_backend=None):
         self.config = config
+        self._surface_backend = surface_backend          # None -> snapshots.HipBackend
         self.store = FrameStore(data_dir or config.data_dir)
         self._bridge_backend = bridge_backend            # None -> HipBridgeBackend / HipCandleBackend on first use
         self._candle_backend = candle_backend
@@ -182,6 +184,33 @@ class CompleteOptimizedPipeline:
         return {"success": ok > 0, "batch_id": batch_id, "symbols_processed": ok, "total_input": total_in,
                 "total_output": total_out, "duration": duration}
 
+    def run_surfaces(self) -> dict:
+        """Per-minute IV surface snapshots: every symbol of interpolated_trading_tickers is pivoted
+        into one (expiry x strike) grid per underlying and minute, each grid goes through the surface engine, and one
+        `iv_surfaces` table per underlying is written (columns underlying, date, spot, tenor, moneyness, iv, status)."""
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder
+        print("\nSURFACES: PER-MINUTE IV SURFACE SNAPSHOTS (MI355X engine)")
+        print("-" * 40)
+        symbols = self.store.symbols("interpolated_trading_tickers")
+        frames = [f for f in (self.store.read_output(s) for s in symbols) if f is not None and not f.empty]
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for surfaces"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_snap = 0
+        for res in results:
+            table = builder.to_frame([res])
+            self.store.write_table(SURFACE_TABLE, res.underlying, table)
+            n = int(table["date"].nunique())
+            n_snap += n
+            print(f"  {res.underlying}: {len(res.expiries)} expiries x {len(res.strikes)} strikes, {n} snapshots")
+        skipped = results[0].skipped_symbols if results else 0
+        duration = time.time() - start
+        print(f"\nSURFACES COMPLETE: {duration:.1f}s, underlyings {len(results)}, snapshots {n_snap:,}, skipped symbols {skipped}")
+        return {"success": n_snap > 0, "underlyings": len(results), "snapshots": n_snap, "skipped_symbols": skipped,
+                "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -213,9 +242,9 @@ class CompleteOptimizedPipeline:
         pass
 
 
-def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None):
+def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -226,7 +255,7 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
     try:
         config = get_config()
         pipeline = CompleteOptimizedPipeline(config, data_dir=args.data_dir, backend=backend, bridge_backend=bridge_backend,
-                                             candle_backend=candle_backend, seed=seed)
+                                             candle_backend=candle_backend, seed=seed, surface_backend=surface_backend)
         if args.synthetic:
             for i in range(args.synthetic):
                 sym = f"btc-20mar23-{20000 + 500 * i}-c"
@@ -250,6 +279,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_task1_interpolation(symbols)
             elif args.task == "bridge":
                 result = pipeline.run_data_bridge(symbols)
+            elif args.task == "surfaces":
+                result = pipeline.run_surfaces()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

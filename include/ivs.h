@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define IVS_ABI_VERSION 3
+#define IVS_ABI_VERSION 4
 
 /* interpolation methods: the pandas method names that core.py:61 forwards
  * (`merged[col].interpolate(method=self.method)`) and that this engine implements */
@@ -236,6 +236,38 @@ int ivs_surface_batch_f64(const double* K, const int64_t* k_off, int64_t k_strid
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Per-minute surface snapshots of ONE underlying from its interpolated option chain (ABI 4; DESIGN.md section 8, rules
+ * S1-S8): the input of ivs_surface_batch_f64 -- sigma, T and the strike query grid of every minute -- assembled on the device
+ * from the rows of `interpolated_trading_tickers`.  The host does the per-contract bookkeeping (symbol parsing, expiry
+ * instants, the strike axis, the cell table); the kernel reads every row once and writes every cell once:
+ *
+ *   date_ns, iv, underlying [n_rows]   the rows of the underlying's C contracts, contract after contract (CSR row_off [C+1]),
+ *                                      sorted by date inside a contract (ties in input order)
+ *   cells [nT*nK][2] (int32)           contract of cell e*nK + k: [0] the call, [1] the put, -1 = none
+ *   strike [nK]                        the strike axis (ascending); expiry_ns [nT] = E_e, ascending
+ *   t0_ns, n_snapshots                 snapshot b is the minute [t0 + b*60 s, t0 + (b+1)*60 s)
+ *   sigma [B][nT][nK]                  S5/S6: the last row of the minute per contract (NaN iv = absent); both sides -> the put
+ *                                      iff strike < the put row's underlying price, else the call; NaN where no side is
+ *                                      present or the expiry has passed (T <= 0)
+ *   T [B][nT]                          (E_e - t_b) / (365 days), also for passed expiries
+ *   spot [B], quotes [B] (int32)       S7: the underlying price of the row behind the first quoted cell in (expiry, strike)
+ *                                      order (NaN if none), the number of quoted cells
+ *   moneyness [mK], kq_empty, Kq [B][mK]   optional (Kq == NULL skips): Kq[b] = spot[b] * moneyness, or kq_empty *
+ *                                      moneyness where spot[b] is NaN
+ * Every output element is written, bitwise deterministically (plain stores, no atomics).  nT <= 32 (the surface engine's
+ * limit) and int32 tables (C, nT*nK, B / minute tile) are checked: IVS_ERANGE.  No workspace.
+ */
+typedef struct ivs_snapshot_args {
+    const int64_t* date_ns; const double* iv; const double* underlying; int64_t n_rows;
+    const int64_t* row_off; int64_t n_contracts;
+    const int32_t* cells; const double* strike; const int64_t* expiry_ns; int32_t nT, nK;
+    int64_t t0_ns, n_snapshots;
+    const double* moneyness; int32_t mK; double kq_empty;
+    double* sigma; double* T; double* spot; int32_t* quotes; double* Kq;
+} ivs_snapshot_args;
+int ivs_snapshot_assemble_f64(const ivs_snapshot_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -282,7 +314,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
                                const uint32_t* words, int64_t n_words, double* out, uint8_t* valid, int64_t* rng_tail,
                                void* workspace, size_t workspace_bytes, void* stream);
 
-/* name of the kernel the last ivs_surface_batch_f64 call on this thread dispatched to (host string) */
+/* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 call on this thread dispatched to (host string) */
 const char* ivs_last_kernel(void);
 
 /*

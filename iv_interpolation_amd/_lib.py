@@ -21,7 +21,7 @@ def flag_map_groups(n: int) -> int:
     """IVS_FLAG_MAP_GROUPS(n): tuning override of the 64x16 kernel's surface -> workgroup mapping (0 = default)."""
     return (int(n) & 0xff) << 8
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # pandas method names (reference core.py:61 forwards self.method) -> engine codes
 NEAREST, ZERO, PCHIP, AKIMA, FROM_DERIVATIVES = 4, 5, 6, 7, 8
@@ -76,6 +76,16 @@ class FrameArgs(C.Structure):
                 ("ch_iv", _i32), ("ch_underlying", _i32), ("ch_ttm", _i32), ("greeks", _p), ("greeks_stride", _i64)]
 
 
+class SnapshotArgs(C.Structure):
+    """ivs_snapshot_args of include/ivs.h (field for field)."""
+    _fields_ = [("date_ns", _p), ("iv", _p), ("underlying", _p), ("n_rows", _i64),
+                ("row_off", _p), ("n_contracts", _i64),
+                ("cells", _p), ("strike", _p), ("expiry_ns", _p), ("nT", _i32), ("nK", _i32),
+                ("t0_ns", _i64), ("n_snapshots", _i64),
+                ("moneyness", _p), ("mK", _i32), ("kq_empty", C.c_double),
+                ("sigma", _p), ("T", _p), ("spot", _p), ("quotes", _p), ("Kq", _p)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -104,6 +114,7 @@ SIGNATURES = {
     "ivs_debug_last_grid": (_i64, []),
     "ivs_debug_mode_offset": (_i64, []),
     "ivs_surface_workspace_bytes": (_sz, [_i64, _i32]),
+    "ivs_snapshot_assemble_f64": (C.c_int, [C.POINTER(SnapshotArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }

@@ -12,6 +12,7 @@
 #include "ivs_candles.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
+#include "ivs_snapshot.hpp"
 #include "ivs_surface_dense.hpp"
 #include "ivs_surface_dense_var2.hpp"
 #include "ivs_surface_pass.hpp"
@@ -320,6 +321,47 @@ int ivs_frame_columns_f64(const ivs_frame_args* a, void* workspace, size_t works
         default: hipLaunchKernelGGL(ivs::frame_fused_kernel<2>, fgrid, dim3(256), 0, st, f, p); break;
     }
     return check_launch("frame_fused_kernel");
+}
+
+int ivs_snapshot_assemble_f64(const ivs_snapshot_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_snapshot_assemble_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->n_rows < 0 || a->n_contracts < 0 || a->nT < 0 || a->nK < 0 || a->n_snapshots < 0 || a->mK < 0)
+        return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->nT > 32) return fail(IVS_ERANGE, "%s: nT=%d expiries exceed the surface engine's 32", fn, a->nT);
+    if (a->n_snapshots == 0) return IVS_OK;
+    if (a->nT < 1 || a->nK < 1) return fail(IVS_ERANGE, "%s: nT=%d x nK=%d: empty axis", fn, a->nT, a->nK);
+    if (!a->cells || !a->strike || !a->expiry_ns || !a->row_off || !a->sigma || !a->T || !a->spot || !a->quotes)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (a->n_rows > 0 && (!a->date_ns || !a->iv || !a->underlying)) return fail(IVS_EINVAL, "%s: null row columns", fn);
+    if (a->Kq && (!a->moneyness || a->mK < 1)) return fail(IVS_EINVAL, "%s: Kq needs moneyness [mK >= 1]", fn);
+    if (a->n_contracts > 0x7fffffffLL || (int64_t)a->nT * a->nK > 0x7fffffffLL)
+        return fail(IVS_ERANGE, "%s: %lld contracts / %lld cells exceed the int32 tables", fn, (long long)a->n_contracts,
+                    (long long)a->nT * a->nK);
+    int dev, cus;
+    current_device(dev, cus);
+    // minutes per workgroup: enough workgroups for ~2 per CU, at least 8 minutes to amortise the per-tile row search
+    int64_t tile = (a->n_snapshots + 2LL * cus - 1) / (2LL * cus);
+    tile = tile < 8 ? 8 : (tile > ivs::SN_MAX_TILE ? ivs::SN_MAX_TILE : tile);
+    const int64_t n_tiles = (a->n_snapshots + tile - 1) / tile;
+    if (n_tiles > 0x7fffffffLL || a->n_snapshots > 0x7fffffffLL) return fail(IVS_ERANGE, "%s: %lld snapshots exceed one launch", fn, (long long)a->n_snapshots);
+    const int64_t ncell = (int64_t)a->nT * a->nK;
+    int waves = (int)((ncell + 63) / 64);
+    waves = waves > ivs::SN_MAX_WAVES ? ivs::SN_MAX_WAVES : waves;
+    ivs::SnapshotParams p{};
+    p.date = a->date_ns; p.iv = a->iv; p.und = a->underlying; p.row_off = a->row_off;
+    p.cells = a->cells; p.strike = a->strike; p.expiry = a->expiry_ns;
+    p.moneyness = a->moneyness; p.mK = a->mK; p.kq_empty = a->kq_empty;
+    p.t0 = a->t0_ns; p.B = a->n_snapshots; p.nT = a->nT; p.nK = a->nK;
+    p.tile = (int32_t)tile; p.n_tiles = (int32_t)n_tiles; p.n_waves = waves;
+    p.sigma = a->sigma; p.T = a->T; p.spot = a->spot; p.quotes = a->quotes; p.Kq = a->Kq;
+    hipLaunchKernelGGL(ivs::snapshot_assemble_kernel, dim3((unsigned)n_tiles), dim3((unsigned)(waves * 64)), 0,
+                       static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "snapshot_assemble_kernel";
+    return check_launch("snapshot_assemble_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

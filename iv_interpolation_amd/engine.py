@@ -140,6 +140,57 @@ def surface_batch(K, T, sigma, Kq, Tq, method="linear", *, k_off=None, nK_max: O
     return out, status
 
 
+def snapshot_assemble(date_ns, iv, underlying, row_off, cells, strike, expiry_ns, t0_ns: int, n_snapshots: int,
+                      moneyness=None, kq_empty: float = 0.0, *, out=None, stream=None):
+    """Per-minute snapshot arrays of ONE underlying from its interpolated chain (ivs_snapshot_assemble_f64; rules S4-S7
+    of DESIGN.md section 8).  Rows: date_ns int64, iv / underlying float64 [n_rows], contract after contract (row_off
+    int64 [C+1]), date-sorted inside a contract; cells int32 [nT*nK, 2] (call / put contract, -1 = none); strike float64
+    [nK]; expiry_ns int64 [nT]; all CUDA tensors.  moneyness float64 [mK] or None switches the Kq output on.
+    `out`: optional dict of preallocated outputs (keys sigma [B,nT,nK], T [B,nT], spot [B], quotes int32 [B], Kq [B,mK]).
+    Returns dict(sigma, T, spot, quotes, Kq) of device tensors (Kq None without moneyness)."""
+    torch = require_device()
+    lib = _lib.load()
+    iv = _f64(torch, iv, "iv"); underlying = _f64(torch, underlying, "underlying"); strike = _f64(torch, strike, "strike")
+    for t, name, dt in ((date_ns, "date_ns", torch.int64), (row_off, "row_off", torch.int64), (cells, "cells", torch.int32),
+                        (expiry_ns, "expiry_ns", torch.int64)):
+        if t.dtype != dt or not t.is_cuda:
+            raise TypeError(f"{name} must be a CUDA {dt} tensor")
+    date_ns, row_off, cells, expiry_ns = date_ns.contiguous(), row_off.contiguous(), cells.contiguous(), expiry_ns.contiguous()
+    n = iv.numel()
+    if date_ns.numel() != n or underlying.numel() != n:
+        raise ValueError("date_ns, iv and underlying must have one entry per row")
+    nK, nT, B = strike.numel(), expiry_ns.numel(), int(n_snapshots)
+    if cells.numel() != 2 * nT * nK:
+        raise ValueError(f"cells must be [nT*nK, 2] = [{nT * nK}, 2]")
+    if moneyness is not None:
+        moneyness = _f64(torch, moneyness, "moneyness")
+    mK = 0 if moneyness is None else moneyness.numel()
+    dev = iv.device
+    out = dict(out or {})
+    shapes = {"sigma": ((B, nT, nK), torch.float64), "T": ((B, nT), torch.float64), "spot": ((B,), torch.float64),
+              "quotes": ((B,), torch.int32), "Kq": ((B, mK), torch.float64)}
+    for k, (shape, dt) in shapes.items():
+        if k == "Kq" and moneyness is None:
+            out[k] = None
+            continue
+        t = out.get(k)
+        if t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=dev)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    a = _lib.SnapshotArgs()
+    a.date_ns, a.iv, a.underlying, a.n_rows = _ptr(date_ns), _ptr(iv), _ptr(underlying), n
+    a.row_off, a.n_contracts = _ptr(row_off), row_off.numel() - 1
+    a.cells, a.strike, a.expiry_ns, a.nT, a.nK = _ptr(cells), _ptr(strike), _ptr(expiry_ns), nT, nK
+    a.t0_ns, a.n_snapshots = int(t0_ns), B
+    a.moneyness, a.mK, a.kq_empty = _ptr(moneyness), mK, float(kq_empty)
+    a.sigma, a.T, a.spot, a.quotes, a.Kq = (_ptr(out[k]) for k in ("sigma", "T", "spot", "quotes", "Kq"))
+    rc = lib.ivs_snapshot_assemble_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, date_ns, iv, underlying, row_off, cells, strike, expiry_ns, moneyness, *out.values())
+    _lib.check(rc, "ivs_snapshot_assemble_f64")
+    return out
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -86,3 +86,50 @@ def synthetic_symbol(symbol: str, n_hours: int = 48, seed: int = 0, start: str =
         "mark_price": 0.03 + r.normal(0, 0.001, n_hours), "index_price": spot + r.normal(0, 5, n_hours),
         "volume": r.uniform(0, 10, n_hours).round(3), "quote_volume": r.uniform(0, 1e5, n_hours).round(1),
         "record_time": (dates.asi8 // 10**6).astype(np.float64)})[SOURCE_COLUMNS]
+
+
+def synthetic_chain(underlying: str = "btc", expiry_days=(2, 9, 30), strikes=(22000.0, 24000.0, 25000.0, 26000.0, 28000.0),
+                    n_hours: int = 24, seed: int = 0, start: str = "2023-03-01", missing: float = 0.0) -> List[pd.DataFrame]:
+    """An hourly option chain of one underlying: one frame per contract (SOURCE_COLUMNS, symbols in the reference's
+    `<underlying>-<ddmonyy>-<strike>-<c|p>` convention), calls and puts at every listed strike of every expiry.
+
+    Expiry i is at `start + expiry_days[i]` days; a contract quotes every hour before its expiry, with
+    time_to_maturity = (E - date) / 365 days exactly.  underlying_price is the expiry's forward F = S exp(0.03 T) on one
+    random-walk spot path; iv is an SVI-like smile in k = ln(K / F) per expiry, the put quoted 2-4 vol points above the
+    call at the same strike (so that taking the wrong side shows in the values).  `missing`: the fraction of strikes left
+    unlisted per expiry (random, at least one strike stays)."""
+    r = np.random.default_rng(seed)
+    t0 = pd.Timestamp(start)
+    dates = pd.date_range(t0, periods=n_hours, freq="1h")
+    d_ns = dates.as_unit("ns").asi8
+    spot = 25000.0 * np.exp(np.cumsum(r.normal(0, 2e-3, n_hours)))
+    year = 365 * 86400 * 10**9
+    strikes = np.asarray(strikes, np.float64)
+    frames = []
+    for days in expiry_days:
+        E = t0 + pd.Timedelta(days=float(days))
+        E_ns = E.as_unit("ns").value
+        label = E.strftime("%d%b%y").lower()
+        a, b, rho, mu, s = r.uniform(.15, .4), r.uniform(.05, .25), r.uniform(-.7, -.1), r.normal(0, .03), r.uniform(.1, .3)
+        listed = strikes[r.random(len(strikes)) >= missing] if missing > 0 else strikes
+        if len(listed) == 0:
+            listed = strikes[:1]
+        live = d_ns < E_ns
+        if not live.any():
+            continue
+        ttm = (E_ns - d_ns[live]) / year
+        fwd = spot[live] * np.exp(0.03 * ttm)
+        for K in listed:
+            k = np.log(K / fwd)
+            base = np.sqrt(a + b * (rho * (k - mu) + np.sqrt((k - mu) ** 2 + s ** 2)))
+            for side in ("c", "p"):
+                n = int(live.sum())
+                iv = base + r.normal(0, 0.002, n) + (r.uniform(0.02, 0.04) if side == "p" else 0.0)
+                sym = f"{underlying}-{label}-{K:g}-{side}"
+                frames.append(pd.DataFrame({
+                    "symbol": sym, "date": dates[live], "iv": iv, "underlying_price": fwd, "time_to_maturity": ttm,
+                    "strike": K, "callput": side, "interest_rate": 0.03,
+                    "mark_price": np.abs(r.normal(0.05, 0.01, n)), "index_price": spot[live],
+                    "volume": r.uniform(0, 10, n).round(3), "quote_volume": r.uniform(0, 1e5, n).round(1),
+                    "record_time": (d_ns[live] // 10**6).astype(np.float64)})[SOURCE_COLUMNS])
+    return frames

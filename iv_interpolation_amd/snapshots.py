@@ -1,0 +1,225 @@
+"""Per-minute IV surface snapshots from the interpolated option chain (rules S1-S8).
+
+The 1-D stage turns every contract's hourly quotes into a minute series (``interpolated_trading_tickers``); this module
+pivots those series into one (expiry x strike) quote grid per underlying and minute and sends the grids through the
+existing surface path (``engine.surface_batch``):
+
+    from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder
+    b = SnapshotSurfaceBuilder(method="linear")
+    res = b.build(long_frame)            # or a list of per-contract frames; one result per underlying
+    df = b.to_frame(res)                 # underlying, date, spot, tenor, moneyness, iv, status
+
+The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
+NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
+counts, spot and the strike query grid -- runs in one HIP kernel per underlying (ivs_snapshot_assemble_f64)."""
+from __future__ import annotations
+
+import re
+from dataclasses import dataclass
+from typing import List, Sequence, Union
+
+import numpy as np
+import pandas as pd
+
+from . import synth
+
+YEAR_NS = 365 * 86400 * 10**9       # S2: E_c = date + time_to_maturity x YEAR, YEAR = 365 days (the synthetic data's convention)
+MINUTE_NS = 60 * 10**9
+MAX_EXPIRIES = 32                   # the surface engine's nT limit
+COLUMNS = ["symbol", "date", "iv", "underlying_price", "time_to_maturity", "strike", "callput"]
+_SYMBOL = re.compile(r"([^-]+)-([^-]+)-([0-9]+(?:\.[0-9]+)?)-([cp])", re.IGNORECASE)
+
+
+@dataclass
+class SnapshotSurfaces:
+    """One underlying's snapshots.  Arrays T, sigma, spot, quotes, Kq, out, status are device tensors with the HIP
+    backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B] snapshot instants t_b
+    expiries: List[str]              # [nT] expiry labels, in axis order
+    expiry_ns: np.ndarray            # [nT] E_e (int64 ns)
+    strikes: np.ndarray              # [nK] strike axis
+    moneyness: np.ndarray            # [mK]
+    tenors: np.ndarray               # [mT] Tq
+    T: object                        # [B, nT]
+    sigma: object                    # [B, nT, nK]
+    spot: object                     # [B]
+    quotes: object                   # [B] int32
+    Kq: object                       # [B, mK]
+    out: object                      # [B, mT, mK]
+    status: object                   # [B]
+    skipped_symbols: int             # contracts of the whole build() call skipped by rule S1
+
+
+class HipBackend:
+    """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
+    HIP device.  Results stay on the device."""
+
+    def __init__(self, stream=None):
+        self.stream = stream
+
+    def assemble(self, date_ns, iv, underlying, row_off, cells, strikes, expiry_ns, t0_ns, n_snapshots, moneyness, kq_empty):
+        from . import engine
+        torch = engine.require_device()
+        d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+        return engine.snapshot_assemble(d(date_ns), d(iv), d(underlying), d(row_off), d(cells), d(strikes), d(expiry_ns),
+                                        t0_ns, n_snapshots, d(moneyness), kq_empty, stream=self.stream)
+
+    def surface_batch(self, K, T, sigma, Kq, Tq, method):
+        from . import engine
+        torch = engine.require_device()
+        return engine.surface_batch(torch.from_numpy(np.ascontiguousarray(K)).cuda(), T, sigma, Kq,
+                                    torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), method, stream=self.stream)
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _int_median(v: np.ndarray) -> int:
+    """Median of int64 ns instants without leaving integers: the middle value, or the lower middle plus half the gap
+    (floored) for an even count."""
+    v = np.sort(v)
+    n = len(v)
+    lo = int(v[(n - 1) // 2])
+    return lo if n % 2 else lo + (int(v[n // 2]) - lo) // 2
+
+
+class SnapshotSurfaceBuilder:
+    def __init__(self, method: str = "linear", moneyness=None, tenors=None, backend=None):
+        m_def, t_def = synth.query_grids(64, 16)
+        self.method = method
+        self.moneyness = np.ascontiguousarray(m_def if moneyness is None else moneyness, np.float64)
+        self.tenors = np.ascontiguousarray(t_def if tenors is None else tenors, np.float64)
+        self._backend = backend
+
+    # ------------------------------------------------------------------ input
+    @staticmethod
+    def _long(data: Union[pd.DataFrame, Sequence[pd.DataFrame]]) -> pd.DataFrame:
+        if isinstance(data, pd.DataFrame):
+            frames = [data]
+        else:
+            frames = [f for f in data if f is not None and len(f)]
+        if not frames:
+            return pd.DataFrame({c: [] for c in COLUMNS})
+        for f in frames:
+            for c in COLUMNS:
+                if c not in f.columns:
+                    raise KeyError(c)
+        if len(frames) == 1:
+            return frames[0][COLUMNS]
+        return pd.concat([f[COLUMNS] for f in frames], ignore_index=True)
+
+    # ------------------------------------------------------------------ build
+    def build(self, data) -> List[SnapshotSurfaces]:
+        """Snapshots of every underlying in `data` (a long frame or a list of per-contract frames), in underlying order."""
+        df = self._long(data)
+        be = self._backend or HipBackend()
+        d_idx = pd.DatetimeIndex(pd.to_datetime(df["date"]))
+        tz = d_idx.tz
+        ns_all = d_idx.as_unit("ns").asi8
+        codes, syms = pd.factorize(df["symbol"], sort=True)          # contract = distinct symbol (S1)
+        ok = (codes >= 0) & ~np.asarray(d_idx.isna())
+        rows = np.flatnonzero(ok)
+        if len(rows) == 0:
+            return []
+        c_r, n_r = codes[rows], ns_all[rows]
+        if len(rows) > 1:
+            dc = np.diff(c_r)
+            if not np.all((dc > 0) | ((dc == 0) & (np.diff(n_r) >= 0))):  # already (symbol, date)-ordered: keep it
+                o = np.lexsort((n_r, c_r))                                 # stable: duplicate dates keep input order
+                rows, c_r, n_r = rows[o], c_r[o], n_r[o]
+        C = len(syms)
+        row_off = np.zeros(C + 1, np.int64)
+        np.cumsum(np.bincount(c_r, minlength=C), out=row_off[1:])
+        has = row_off[1:] > row_off[:-1]
+        first = rows[np.minimum(row_off[:-1], len(rows) - 1)]      # each contract's first row in date order
+
+        # S1: parse the symbols (per contract), strike / side / E_c from the first row
+        parsed = pd.Series(np.asarray(syms, dtype=object)).astype(str).str.fullmatch(_SYMBOL.pattern, flags=re.IGNORECASE)
+        parts = pd.Series(np.asarray(syms, dtype=object)).astype(str).str.lower().str.split("-")
+        cp = df["callput"].to_numpy()[first]
+        side = pd.Series(cp, dtype=object).astype(str).str[:1].str.lower().to_numpy()
+        strike = pd.to_numeric(df["strike"], errors="coerce").to_numpy(np.float64)[first]
+        ttm = pd.to_numeric(df["time_to_maturity"], errors="coerce").to_numpy(np.float64)[first]
+        good = has & parsed.to_numpy(bool) & np.isin(side, ["c", "p"]) & ~np.isnan(strike) & np.isfinite(ttm)
+        skipped = int(np.count_nonzero(has & ~good))
+        if not good.any():
+            return []
+        e_c = np.zeros(C, np.int64)
+        e_c[good] = ns_all[first[good]] + np.rint(ttm[good] * float(YEAR_NS)).astype(np.int64)
+        und = np.array([p[0] if g else "" for p, g in zip(parts, good)], dtype=object)
+        lab = np.array([p[1] if g else "" for p, g in zip(parts, good)], dtype=object)
+        iv_all = pd.to_numeric(df["iv"], errors="coerce").to_numpy(np.float64)
+        up_all = pd.to_numeric(df["underlying_price"], errors="coerce").to_numpy(np.float64)
+
+        results = []
+        for u in sorted(set(und[good])):
+            cs = np.flatnonzero(good & (und == u))                           # contracts of u, in symbol order
+            labels = sorted(set(lab[cs]))
+            e_e = {lb: _int_median(e_c[cs[lab[cs] == lb]]) for lb in labels}
+            exp = sorted(labels, key=lambda lb: (e_e[lb], lb))
+            if len(exp) > MAX_EXPIRIES:
+                raise ValueError(f"underlying {u!r} has {len(exp)} expiries; the surface engine takes at most {MAX_EXPIRIES}")
+            K = np.unique(strike[cs])
+            nT, nK = len(exp), len(K)
+            e_of = {lb: i for i, lb in enumerate(exp)}
+            e_idx = np.array([e_of[lb] for lb in lab[cs]], np.int64)
+            k_idx = np.searchsorted(K, strike[cs])
+            s_idx = (side[cs] == "p").astype(np.int64)
+            slot = (e_idx * nK + k_idx) * 2 + s_idx
+            if len(np.unique(slot)) != len(slot):
+                _, inv, cnt = np.unique(slot, return_inverse=True, return_counts=True)
+                dup = [str(syms[c]) for c in cs[cnt[inv] > 1]]
+                raise ValueError(f"underlying {u!r}: several contracts for one (expiry, strike, side): {dup[:4]}")
+            cells = np.full(nT * nK * 2, -1, np.int32)
+            cells[slot] = np.arange(len(cs), dtype=np.int32)
+            lens = row_off[cs + 1] - row_off[cs]
+            loc_off = np.zeros(len(cs) + 1, np.int64)
+            np.cumsum(lens, out=loc_off[1:])
+            if np.all(np.diff(cs) == 1):
+                sel = rows[row_off[cs[0]]:row_off[cs[-1] + 1]]
+            else:
+                sel = rows[np.concatenate([np.arange(row_off[c], row_off[c + 1]) for c in cs])]
+            date = ns_all[sel]
+            t0 = int(date.min()) // MINUTE_NS * MINUTE_NS                    # S4
+            B = (int(date.max()) - t0) // MINUTE_NS + 1
+            expiry_ns = np.array([e_e[lb] for lb in exp], np.int64)
+            kq_empty = float(K[(nK - 1) // 2])                               # S8: empty snapshots query around the middle strike
+            a = be.assemble(date, iv_all[sel], up_all[sel], loc_off, cells.reshape(-1, 2), K, expiry_ns, t0, B,
+                            self.moneyness, kq_empty)
+            out, status = be.surface_batch(K, a["T"], a["sigma"], a["Kq"], self.tenors, self.method)
+            dates = pd.DatetimeIndex(t0 + MINUTE_NS * np.arange(B, dtype=np.int64), dtype="datetime64[ns]")
+            if tz is not None:
+                dates = dates.tz_localize("UTC").tz_convert(tz)
+            results.append(SnapshotSurfaces(u, dates, exp, expiry_ns, K, self.moneyness, self.tenors, a["T"], a["sigma"],
+                                            a["spot"], a["quotes"], a["Kq"], out, status, skipped))
+        return results
+
+    # ------------------------------------------------------------------ output
+    @staticmethod
+    def to_frame(results: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+        """Long frame of the surfaces of every snapshot with quotes > 0: columns underlying, date, spot, tenor, moneyness,
+        iv, status, ordered by (underlying, date, tenor, moneyness)."""
+        parts = []
+        for r in results:
+            q = _host(r.quotes)
+            keep = np.flatnonzero(q > 0)
+            out = _host(r.out)[keep]                                         # [n, mT, mK]
+            n, mT, mK = out.shape
+            per = mT * mK
+            parts.append(pd.DataFrame({
+                "underlying": r.underlying,
+                "date": r.dates[keep].repeat(per),
+                "spot": np.repeat(_host(r.spot)[keep], per),
+                "tenor": np.tile(np.repeat(r.tenors, mK), n),
+                "moneyness": np.tile(np.tile(r.moneyness, mT), n),
+                "iv": out.reshape(-1),
+                "status": np.repeat(_host(r.status)[keep], per)}))
+        if not parts:
+            return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"),
+                                 "spot": pd.Series(dtype=np.float64), "tenor": pd.Series(dtype=np.float64),
+                                 "moneyness": pd.Series(dtype=np.float64), "iv": pd.Series(dtype=np.float64),
+                                 "status": pd.Series(dtype=np.int32)})
+        df = pd.concat(parts, ignore_index=True)
+        return df.sort_values(["underlying", "date", "tenor", "moneyness"], kind="stable").reset_index(drop=True)
