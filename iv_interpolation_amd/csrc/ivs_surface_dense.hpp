@@ -290,9 +290,6 @@ __device__ __forceinline__ double pchip_edge(double m0, double m1, double ea, do
     return (d * m0 > 0.0) ? r : 0.0;                       // branch-free on purpose (selects)
 }
 // akima (scipy _cubic.py:510-541): secants ma..md = m_{i-2}, m_{i-1}, m_i, m_{i+1}
-#ifndef IVS_AKIMA_ROLL
-#define IVS_AKIMA_ROLL 1      // akima's maturity slopes formed while the output rows are walked (dense_maturity_pass)
-#endif
 __device__ __forceinline__ double akima_f12(double ma, double mb, double mc, double md) {
     return __builtin_fabs(md - mc) + __builtin_fabs(mb - ma);
 }
@@ -395,86 +392,37 @@ __device__ __forceinline__ void dense_strike_slopes_local(const double* Y, doubl
     }
 }
 
-// The same slopes in the maturity direction: 16 knots per lane in registers, tables TT[i] = {r0, r1, r2, -}.
-template <int METHOD, class TP>
-__device__ __forceinline__ void dense_maturity_slopes_local(const double (&z)[DT], TP TT, double (&s)[DT]) {
-    constexpr bool AK = METHOD == IVS_AKIMA;
+// pchip's slopes in the maturity direction: 16 knots per lane in registers, tables TT[i] = {r0, r1, r2, -}.  (akima forms
+// its maturity slopes while the output rows are walked: dense_maturity_pass.)
+template <class TP>
+__device__ __forceinline__ void dense_maturity_slopes_pchip(const double (&z)[DT], TP TT, double (&s)[DT]) {
     auto sec = [&](int i) { return (z[i + 1] - z[i]) * TT[i * 4]; };       // m_i, i = 0..14
-    if (!AK) {
-        double mp = sec(0), mk = sec(1);
-        s[0] = pchip_edge(mp, mk, TT[1], TT[2]);
+    double mp = sec(0), mk = sec(1);
+    s[0] = pchip_edge(mp, mk, TT[1], TT[2]);
 #pragma unroll
-        for (int i = 1; i < DT - 1; ++i) {          // (mp, mk) = (m_{i-1}, m_i)
-            s[i] = pchip_knot(mp, mk, TT[i * 4 + 1], TT[i * 4 + 2]);
-            if (i < DT - 2) { mp = mk; mk = sec(i + 1); }
-            if ((i & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-        }
-        s[DT - 1] = pchip_edge(mk, mp, TT[(DT - 1) * 4 + 1], TT[(DT - 1) * 4 + 2]);
-    } else {
-        const double l1 = 2.0 * sec(0) - sec(1), l0 = 2.0 * l1 - sec(0);                       // m_{-1}, m_{-2}
-        const double r15 = 2.0 * sec(DT - 2) - sec(DT - 3), r16 = 2.0 * r15 - sec(DT - 2);     // m_15, m_16
-        auto secx = [&](int i) {                    // m_i, i = -2..16
-            return i == -2 ? l0 : (i == -1 ? l1 : (i == DT - 1 ? r15 : (i == DT ? r16 : sec(i < 0 ? 0 : (i > DT - 2 ? DT - 2 : i)))));
-        };
-        double fmax = 0.0;
-        {
-            double ma = secx(-2), mb = secx(-1), mc = secx(0);
-#pragma unroll
-            for (int i = 0; i < DT; ++i) {
-                const double md = secx(i + 1);
-                fmax = __builtin_fmax(fmax, akima_f12(ma, mb, mc, md));
-                ma = mb; mb = mc; mc = md;
-            }
-        }
-        const double thr = 1e-9 * fmax;
-        double ma = secx(-2), mb = secx(-1), mc = secx(0);
-#pragma unroll
-        for (int i = 0; i < DT; ++i) {
-            const double md = secx(i + 1);
-            s[i] = akima_knot(ma, mb, mc, md, thr);
-            ma = mb; mb = mc; mc = md;
-            if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
+    for (int i = 1; i < DT - 1; ++i) {          // (mp, mk) = (m_{i-1}, m_i)
+        s[i] = pchip_knot(mp, mk, TT[i * 4 + 1], TT[i * 4 + 2]);
+        if (i < DT - 2) { mp = mk; mk = sec(i + 1); }
+        if ((i & 1) == 1) __builtin_amdgcn_sched_barrier(0);
     }
+    s[DT - 1] = pchip_edge(mk, mp, TT[(DT - 1) * 4 + 1], TT[(DT - 1) * 4 + 2]);
 }
 
-// Run-time maturity count nT (4..16): tables are all-zero beyond nT, so secants beyond the last knot come out 0 and are
-// replaced by akima's linear extension F(i) = 2 F(i-1) - F(i-2); pchip's one-sided rule moves to knot nT - 1.
-template <int METHOD, class TP>
-__device__ __forceinline__ void dense_maturity_slopes_local_rt(const double (&z)[DT], TP TT, double (&s)[DT], int nT) {
-    constexpr bool AK = METHOD == IVS_AKIMA;
+// Run-time maturity count nT (4..16): tables are all-zero beyond nT, so secants beyond the last knot come out 0; the
+// one-sided rule moves to knot nT - 1.
+template <class TP>
+__device__ __forceinline__ void dense_maturity_slopes_pchip_rt(const double (&z)[DT], TP TT, double (&s)[DT], int nT) {
     double F[DT + 3];                               // F[i] = m_{i-2}
 #pragma unroll
     for (int i = 0; i < DT - 1; ++i) F[i + 2] = (z[i + 1] - z[i]) * TT[i * 4];
     F[DT + 1] = 0.0; F[DT + 2] = 0.0; F[0] = 0.0; F[1] = 0.0;
-    if (!AK) {
-        s[0] = pchip_edge(F[2], F[3], TT[1], TT[2]);
+    s[0] = pchip_edge(F[2], F[3], TT[1], TT[2]);
 #pragma unroll
-        for (int i = 1; i < DT; ++i) {
-            const double w1 = TT[i * 4 + 1], w2 = TT[i * 4 + 2];
-            if (i == nT - 1) s[i] = pchip_edge(F[i + 1], F[i], w1, w2);      // wave-uniform branch: one of the two is computed
-            else s[i] = pchip_knot(F[i + 1], F[i + 2], w1, w2);
-            if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
-    } else {
-        F[1] = 2.0 * F[2] - F[3]; F[0] = 2.0 * F[1] - F[2];
-#pragma unroll
-        for (int i = 4; i < DT + 3; ++i) {
-            const int idx = i - 2;
-            F[i] = (idx == nT - 1 || idx == nT) ? 2.0 * F[i - 1] - F[i - 2] : F[i];
-        }
-        double fmax = 0.0;
-#pragma unroll
-        for (int i = 0; i < DT; ++i) {
-            const double f = akima_f12(F[i], F[i + 1], F[i + 2], F[i + 3]);
-            fmax = (i < nT) ? __builtin_fmax(fmax, f) : fmax;
-        }
-        const double thr = 1e-9 * fmax;
-#pragma unroll
-        for (int i = 0; i < DT; ++i) {
-            s[i] = akima_knot(F[i], F[i + 1], F[i + 2], F[i + 3], thr);
-            if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
+    for (int i = 1; i < DT; ++i) {
+        const double w1 = TT[i * 4 + 1], w2 = TT[i * 4 + 2];
+        if (i == nT - 1) s[i] = pchip_edge(F[i + 1], F[i], w1, w2);      // wave-uniform branch: one of the two is computed
+        else s[i] = pchip_knot(F[i + 1], F[i + 2], w1, w2);
+        if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -720,8 +668,7 @@ __device__ __forceinline__ void dense_t_phase(const double* Tb, const double* Tq
 // NTR: run-time maturity count nT_rt (see dense_t_phase): masked system rows, three-tap last row, hold row = nT_rt - 1.
 // SM: TT and W point at the TqShared tables in global memory; every read of them is a scalar load (uniform index),
 // the next row's weights are requested while the current row is combined and stored.
-// AKROLL: akima's slopes formed while the rows are walked (see there); false where the registers are not the limit.
-template <int METHOD, bool WLDS, bool RANGED = false, bool NTR = false, bool SM = false, bool AKROLL = true, class StampFn>
+template <int METHOD, bool WLDS, bool RANGED = false, bool NTR = false, bool SM = false, class StampFn>
 __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const TqTables& tt, const double* TT,
                                                     const double* W, double* outb, int q0, int lane, bool act, int mT,
                                                     int mK, StampFn&& stamp, int row_lo = 0, int row_hi = 0,
@@ -746,31 +693,9 @@ __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const
     int tq = 0;
     double* rp = outb + q0;                                    // row tq of the output block: uniform running pointer
     cdptr wp = cW;                                             // SM: weights of row tq
-#ifdef IVS_PUT_PAIR
-    // A/B variant (verdict r02 item 8): 16 bytes per lane -- rows are stored in PAIRS, lane pair (2i, 2i+1)
-    // swaps one value through a quad_perm DPP move, the even lane writes strikes (2i, 2i+1) of the even row, the odd lane
-    // those of the odd row: half the store instructions, 1 KB per instruction.  Needs mK even and a 16-byte aligned block.
-    const bool pair_ok = !RANGED && (mK & 1) == 0 && ((reinterpret_cast<uintptr_t>(outb + q0) & 15) == 0);      // wave-uniform
-    const int pair_off = (lane & 1) ? lane - 1 : lane - mK;
-    double pend = 0.0;
-#endif
     auto put = [&](int row, double v) {                        // row == tq at every call site
         (void)row;
         if (ABL == 4 && (row & 7) != 0) { asm volatile("" :: "v"(v)); return; }
-#ifdef IVS_PUT_PAIR
-        if (pair_ok) {
-            if (!(tq & 1)) {
-                pend = v;
-                if (tq == mT - 1 && act) rp[lane] = v;         // an odd row count leaves the last row unpaired
-            } else {
-                const double send = (lane & 1) ? pend : v;
-                const double recv = dpp_f64<0xB1>(send, send);       // quad_perm [1, 0, 3, 2]
-                double2 o; o.x = (lane & 1) ? recv : pend; o.y = (lane & 1) ? v : recv;
-                if (act) *reinterpret_cast<double2*>(rp + pair_off) = o;
-            }
-            return;
-        }
-#endif
         if (act) rp[lane] = v;
     };
     auto adv = [&]() { ++tq; rp += mK; wp += 4; };
@@ -807,13 +732,12 @@ __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const
             a2 = readlane_f64(tt.w2, row); a3 = readlane_f64(tt.w3, row);
         }
     };
-    if (METHOD == IVS_AKIMA && IVS_AKIMA_ROLL && AKROLL) {
+    if (METHOD == IVS_AKIMA) {
         // akima, slopes formed WHILE the rows are walked: knot j needs the secants m_{j-2} .. m_{j+1} only, so a window of
         // four secants slides along the 16 knots twice -- once for the row maximum of |m_{j+1} - m_j| + |m_{j-1} - m_{j-2}|
         // (the threshold of the equal-secants rule), once in the row loop, where an interval needs just its two end slopes.
-        // Live: z[16], the window, two slopes -- not s[16] and the 19 secants a common-subexpression pass keeps between the
-        // two loops of dense_maturity_slopes_local (240 VGPRs on the run-time-shape kernels, 2 wavefronts per SIMD).  Same
-        // expressions in the same order: bit-identical.
+        // Live: z[16], the window, two slopes -- not s[16] and the 19 secants a common-subexpression pass kept between the
+        // two loops of the all-slopes-first form (240 VGPRs on the run-time-shape kernels, 2 wavefronts per SIMD).
         double zz[DT];
 #pragma unroll
         for (int i = 0; i < DT; ++i) zz[i] = z[i];
@@ -864,13 +788,13 @@ __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const
         double s[DT];
         double prev = 0.0;
         const double pm_last = NTR ? readlane_f64(tt.pm_last, 0) : 0.0;      // uniform -> SGPRs
-        if (d_is_local(METHOD)) {
+        if (METHOD == IVS_PCHIP) {
             if (SM) {
-                if (NTR) dense_maturity_slopes_local_rt<METHOD>(z, cTT, s, nT);
-                else dense_maturity_slopes_local<METHOD>(z, cTT, s);
+                if (NTR) dense_maturity_slopes_pchip_rt(z, cTT, s, nT);
+                else dense_maturity_slopes_pchip(z, cTT, s);
             } else {
-                if (NTR) dense_maturity_slopes_local_rt<METHOD>(z, TT, s, nT);
-                else dense_maturity_slopes_local<METHOD>(z, TT, s);
+                if (NTR) dense_maturity_slopes_pchip_rt(z, TT, s, nT);
+                else dense_maturity_slopes_pchip(z, TT, s);
             }
             // pin the slopes here: otherwise they (and, transitively, the strike evaluation with its 64 gathered
             // operands) are sunk into the row loops below and the live set overflows the register file

@@ -1,8 +1,10 @@
-// Surfaces with MISSING quotes, 64 strikes x 16 maturities, not-a-knot methods: the row-pass form of the masked kernel.
+// Surfaces with MISSING quotes, 64 strikes x 16 maturities, methods with slopes or coefficients (cubic, cubicspline,
+// quadratic, pchip, akima): the row-pass form of the masked kernel.
 //
-// ivs_surface_masked.hpp eliminates every row's own tridiagonal system with TWO lanes per row (from both ends), 32 of 64
-// lanes busy on dependent chains of up to 32 steps, the elimination's c' coefficients in 64 VGPRs: 256 VGPRs, 19.5 KB of
-// LDS, 8 wavefronts per CU, 42 % of the wave time parked on dependent LDS round trips (profiles/r02/final/pmc_nan10.json).
+// A missing quote changes the knot set of its row, so every row has its own tridiagonal system.  Round 2 eliminated it with
+// TWO lanes per row (from both ends) inside surface_masked_kernel: 32 of 64 lanes busy on dependent chains of up to 32 steps,
+// 256 VGPRs, 19.5 KB of LDS, 8 wavefronts per CU, 42 % of the wave time parked on dependent LDS round trips
+// (profiles/r02/final/pmc_nan10.json).
 // Here the 16 rows are processed in two PASSES of 8 rows and a row's compacted system is solved by EIGHT lanes, lane =
 // (row of the pass, segment of 8 compacted knots), as a segmented two-level elimination:
 //   1. every lane normalises its (up to) 8 system rows (1 / b_i) and multiplies the 2 x 2 Moebius matrices of the pivot
@@ -170,10 +172,10 @@ __device__ __forceinline__ void masked_solve8(const double* YC, double* XS, cons
 }
 
 // Local-slope methods (pchip, akima) on the same layout: lane = (row of the pass, segment of 8 compacted knots), the 8 slopes
-// of the segment from the 11 secants around it (2 knots of either neighbour), no system to solve.  Formulas of the
-// lane-per-knot form in ivs_surface_masked.hpp (pchip: weighted harmonic mean, one-sided three-point rule at knots 0 and
-// n - 1, the secant for n == 2; akima: secants extended linearly two steps beyond either end, the row maximum of
-// |m_{k+1} - m_k| + |m_{k-1} - m_{k-2}| over the row's 8 lanes by three DPP moves).  XS: strikes on entry, slopes on exit.
+// of the segment from the 11 secants around it (2 knots of either neighbour), no system to solve.  pchip:
+// weighted harmonic mean, one-sided three-point rule at knots 0 and n - 1, the secant for n == 2; akima: secants extended
+// linearly two steps beyond either end, the row maximum of |m_{k+1} - m_k| + |m_{k-1} - m_{k-2}| over the row's 8 lanes by
+// three DPP moves.  XS: strikes on entry, slopes on exit.
 template <int METHOD>
 __device__ __forceinline__ void masked_local8(const double* YC, double* XS, const int* NROW, int lane) {
     constexpr bool AK = METHOD == IVS_AKIMA;
@@ -354,11 +356,7 @@ __global__ __launch_bounds__(64, 3) void surface_masked_pass_kernel(SurfaceParam
 #pragma unroll
                 for (int st = 4; st >= 1; st >>= 1) if (Ksh[jf + st] <= xq) jf += st;
             }
-#ifndef IVS_MP_ABL
-#define IVS_MP_ABL 0      // phase ablations (wrong results, timing only): 1 = no slope solve, 2 = no strike evaluation, 3 = no compaction tables
-#endif
-            if (IVS_MP_ABL == 1) {}
-            else if (LOCAL) masked_local8<METHOD>(YC, XS, NROW, lane);
+            if (LOCAL) masked_local8<METHOD>(YC, XS, NROW, lane);
             else masked_solve8<QUAD>(YC, XS, NROW, lane);
             __syncthreads();
             // ---- strike evaluation of the pass's rows (q-lane): per row one RANK byte away from the full-grid interval
@@ -373,8 +371,7 @@ __global__ __launch_bounds__(64, 3) void surface_masked_pass_kernel(SurfaceParam
                 const MaskedX X{Ksh, IDX + r * DK};
                 const CView Y{YC + r * MK_RS, 1}, S{XS + r * MK_RS, 1};
                 double zz;
-                if (IVS_MP_ABL == 2) zz = Y(lane & 7) + xq;
-                else if (QUAD) {
+                if (QUAD) {
                     // eval_quadratic with the row's strikes read ONCE: the six sites around the interval (x(je-2 .. je+3), je =
                     // min(j, n-2)) hold every site the basis window [q, q+2], q in {je-1, je}, can ask for; the triple end knots
                     // come from the ballot mask.  (eval_quadratic read ~11 strikes per row through the two-level IDX table:

@@ -24,43 +24,28 @@
 // Work distribution: work queues (WorkQueue, ivs_surface_generic.hpp), not static striding.
 // Scope: T and Tq shared by the batch, mK <= 64 (one block of output strikes: the pass structure would recompute the
 // slopes per block), 4..16 maturities, 4..128 strikes; per-surface maturities for `linear` with mT <= 16 (TSH = false);
-// 64 x 16 akima, per-surface maturities of the other methods and wider output grids stay on the one-pass kernels;
+// per-surface maturities of the other methods and wider output grids stay on the one-pass kernels;
 // `quadratic` runs the not-a-knot machinery on its collocation system (QUADM / quad_weights).
 #pragma once
 #include "ivs_surface_dense_var2.hpp"
 #include "ivs_surface_masked.hpp"
 
-#ifndef IVS_PASS_SL
-#define IVS_PASS_SL 8      // knots per segment of the uniform 64 x 16 kernel (8: 12 workgroups / CU, 4: 16)
-#endif
+namespace ivs {
 
-#ifndef IVS_PASS_CAP2
+constexpr int PASS_SL = 8;         // knots per segment
 // workgroups per CU of the 128-strike kernel (LDS admits 9).  Under STATIC striding 9 lost 8.5 % against 8 (one SIMD of
 // every CU carries three wavefronts, its workgroups ran at 2/3 of the others' pace and the launch waited for them); with
 // the work queues the uneven wavefront counts balance out: 184.9 vs 175.9 M surfaces/s for the 65..128 class.
-#define IVS_PASS_CAP2 12
-#endif
-#ifndef IVS_PASS_CHUNK
-#define IVS_PASS_CHUNK 4      // surfaces per work-queue claim
-#endif
-#ifndef IVS_PASS_PFP4
-#define IVS_PASS_PFP4 2
-#endif
-#ifndef IVS_PASS_WIDE
-// A/B variant, REJECTED (round 3, profiles/r03/ab_cfg5_wide_staging_and_ablations.txt): run-time-shape kernels staging their
-// quotes with 16 B per lane (a lane takes TWO neighbouring strikes of a row; 64 strikes: one load covers two rows, 128
-// strikes: one row) instead of one row of 8-byte loads with the lanes beyond n idle.  Half the VMEM and LDS-store
-// instructions per pass, bit-identical results -- and 2-5 % SLOWER in every size class (65..128: 186.7 -> 183.8 M surfaces/s,
-// 8..64: 311.6 -> 298.3): these kernels are bound by their arithmetic phases (the ablations in the same file: K-phase +
-// sweeps cost 25-37 % of the call, the no-math skeleton streams at 5.5-5.7 TB/s), not by load / store instruction issue,
-// and the pair addressing costs 12-16 B of scratch at 168 VGPRs.
-#define IVS_PASS_WIDE 0
-#endif
-namespace ivs {
+constexpr int PASS_CAP2 = 12;
+constexpr int PASS_CHUNK = 4;      // surfaces per work-queue claim
+// The run-time-shape kernels stage their quotes one row of 8-byte loads at a time, the lanes beyond n idle.  16 B per lane (a
+// lane takes two neighbouring strikes) halved the VMEM and LDS-store instructions and was 2-5 % slower in every size class
+// (profiles/r03/ab_cfg5_wide_staging_and_ablations.txt): these kernels are bound by their arithmetic phases.
 
-template <int NKB, int SL = 8>
+template <int NKB>
 struct PassGeom {
-    static constexpr int NSEG = 64 * NKB / SL;     // segments of SL (8 or 4) knots per row
+    static constexpr int SL = PASS_SL;
+    static constexpr int NSEG = 64 * NKB / SL;     // segments of SL knots per row
     static constexpr int RP = 64 / NSEG;           // rows per pass
     static constexpr int NPASS = DT / RP;
     static constexpr int KCAP = 64 * NKB;
@@ -75,7 +60,6 @@ struct PassGeom {
     static constexpr int TS = SL + 2;              // table segment stride (SL entries + 2 spare)
     static constexpr int TN = NSEG * TS;           // one table
     static constexpr int NSCAN = NSEG == 8 ? 3 : 4; // carry scan steps (shift 1, 2, 4[, 8])
-    static_assert(SL == 8 || (SL == 4 && NKB == 1), "segment length");
     static_assert(NSEG == 8 || NSEG == 16, "a row's segments live in one DPP row");
 };
 // 128 strikes, not-a-knot: the in-segment products PI / PSI are not tabulated but rebuilt as running products inside the
@@ -83,49 +67,47 @@ struct PassGeom {
 // the strikes alias the S plane (they are dead before the first sweep writes it): 16 896 -> 13 328 B = 9 -> 11 workgroups per CU.
 template <int NKB> __host__ __device__ constexpr bool pass_runp() { return NKB == 2; }
 constexpr int PASS_TQ_DOUBLES = DT * 4 + D_WLDS_MAX_MT * 4;      // per-surface maturity tables TT + W (TSH = false)
-template <int NKB, bool VAR, int SL = 8, int KIND = 0>      // KIND 0: not-a-knot, 1: lerp, 2: local slopes
+template <int NKB, int KIND = 0>      // KIND 0: not-a-knot, 1: lerp, 2: local slopes
 __host__ __device__ constexpr size_t pass_lds_bytes() {
-    using G = PassGeom<NKB, SL>;
+    using G = PassGeom<NKB>;
     // Y, S planes; AL CP PP QQ PI PSI tables (local slopes: R0 R1 R2); Ksh  (lerp methods: Y plane and Ksh only)
     if (KIND == 0 && pass_runp<NKB>()) return (size_t)(2 * G::PLANE + 4 * G::TN + 2) * 8;
     return KIND == 1 ? (size_t)(G::PLANE + G::KCAP) * 8 : (size_t)(2 * G::PLANE + (KIND == 2 ? 3 : 6) * G::TN + G::KCAP) * 8;
 }
 
-template <int SL> __device__ __forceinline__ int p_tix(int k) { return (k / SL) * (SL + 2) + (k % SL); }
-// S plane, 8-knot segments: 16-byte slot c of segment s sits at c ^ (s >> 1) (conflict-free b128 writes); 4-knot segments
-// need no swizzle (the odd row stride already interleaves the two rows of a 16-lane write group)
-template <int SL, int NKB = 1> __device__ __forceinline__ int p_swz(int k) {
-    return NKB == 2 ? k ^ (((k >> 5) & 3) << 1) : (SL == 8 ? k ^ (((k >> 4) & 3) << 1) : k);
+__device__ __forceinline__ int p_tix(int k) { return (k / PASS_SL) * (PASS_SL + 2) + (k % PASS_SL); }
+// S plane: 16-byte slot c of segment s sits at c ^ (s >> 1) (64 strikes; conflict-free b128 writes) or c ^ (s >> 2) (128)
+template <int NKB> __device__ __forceinline__ int p_swz(int k) {
+    return NKB == 2 ? k ^ (((k >> 5) & 3) << 1) : k ^ (((k >> 4) & 3) << 1);
 }
 // Y plane: swizzled like the S plane for 128 strikes, plain otherwise
 template <int NKB> __device__ __forceinline__ int y_swz(int k) { return NKB == 2 ? k ^ (((k >> 5) & 3) << 1) : k; }
 
-// inclusive prefix / suffix products within aligned groups of SL lanes (several groups per DPP row: a shifted value that
+// inclusive prefix / suffix products within aligned groups of 8 lanes (two groups per DPP row: a shifted value that
 // comes from the neighbouring group is replaced by 1.0)
-template <int SL>
 __device__ __forceinline__ double seg_prefix_prod(double v, int lane) {
-    const int i = lane & (SL - 1);
+    static_assert(PASS_SL == 8, "three shift steps");
+    const int i = lane & 7;
     double t = dpp_f64<DPP_ROW_SHR(1)>(1.0, v); v *= i >= 1 ? t : 1.0;
     t = dpp_f64<DPP_ROW_SHR(2)>(1.0, v); v *= i >= 2 ? t : 1.0;
-    if (SL > 4) { t = dpp_f64<DPP_ROW_SHR(4)>(1.0, v); v *= i >= 4 ? t : 1.0; }
+    t = dpp_f64<DPP_ROW_SHR(4)>(1.0, v); v *= i >= 4 ? t : 1.0;
     return v;
 }
-template <int SL>
 __device__ __forceinline__ double seg_suffix_prod(double v, int lane) {
-    const int i = lane & (SL - 1);
-    double t = dpp_f64<DPP_ROW_SHL(1)>(1.0, v); v *= i <= SL - 2 ? t : 1.0;
-    t = dpp_f64<DPP_ROW_SHL(2)>(1.0, v); v *= i <= SL - 3 ? t : 1.0;
-    if (SL > 4) { t = dpp_f64<DPP_ROW_SHL(4)>(1.0, v); v *= i <= 3 ? t : 1.0; }
+    const int i = lane & 7;
+    double t = dpp_f64<DPP_ROW_SHL(1)>(1.0, v); v *= i <= 6 ? t : 1.0;
+    t = dpp_f64<DPP_ROW_SHL(2)>(1.0, v); v *= i <= 5 ? t : 1.0;
+    t = dpp_f64<DPP_ROW_SHL(4)>(1.0, v); v *= i <= 3 ? t : 1.0;
     return v;
 }
 
 // K-phase: factorisation tables of the not-a-knot system on n knots (n = KCAP when !VAR) at p_tix(k), the segment
 // products P_j = prod(-AL) / Q_j = prod(-CP) of every 8-knot segment, and from them the multipliers of the carry scans
 // (see pass_sweeps).  Ends with the tables visible to every lane.
-template <int NKB, bool VAR, int SL = 8, bool QUADM = false>      // QUADM: the collocation system of the quadratic B-spline instead
+template <int NKB, bool VAR, bool QUADM = false>      // QUADM: the collocation system of the quadratic B-spline instead
 __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int lane, double* TB, double* SCR = nullptr) {
-    using G = PassGeom<NKB, SL>;
-    constexpr int TS = G::TS;
+    using G = PassGeom<NKB>;
+    constexpr int SL = G::SL, TS = G::TS;
     constexpr int TN = G::TN, NSEG = G::NSEG;
     constexpr bool RUNP = pass_runp<NKB>();         // no PI / PSI tables: segment products go through SCR (free LDS), pm_last behind QQ
     double* AL = TB; double* CP = TB + TN; double* PP = TB + 2 * TN; double* QQ = TB + 3 * TN;
@@ -193,11 +175,11 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
             pp = 3.0 * dxc * rdx_prev * rw;                      // * dy_{i-1}
             qq = 3.0 * dxm * rdxc * rw;                          // * dy_i
         }
-        const double pi = seg_prefix_prod<SL>(in ? -al : 1.0, lane);
-        const double psi = seg_suffix_prod<SL>(in ? -cp : 1.0, lane);
+        const double pi = seg_prefix_prod(in ? -al : 1.0, lane);
+        const double psi = seg_suffix_prod(in ? -cp : 1.0, lane);
         {   // beyond n the NEUTRAL row (AL = -1, everything else 0): the forward sweep holds its value, the last system
             // row's CP = 0 cuts the backward recurrence off from whatever lies to its right (see factor_tables_var)
-            const int kl = p_tix<SL>(ir);
+            const int kl = p_tix(ir);
             AL[kl] = in ? al : -1.0; CP[kl] = in ? cp : 0.0; PP[kl] = in ? pp : 0.0; QQ[kl] = in ? qq : 0.0;
             if (RUNP) {
                 if (VAR && last) TB[4 * TN] = pm;
@@ -240,10 +222,10 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
 }
 
 // One pass: slopes of the RP rows staged in Yp -> Sp.  All 64 lanes; no barrier inside (the caller brackets it).
-template <int NKB, bool VAR, int SL = 8, bool QUADM = false>
+template <int NKB, bool VAR, bool QUADM = false>
 __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const double* TB, int lane, int n) {
-    using G = PassGeom<NKB, SL>;
-    constexpr int TN = G::TN, NSEG = G::NSEG, RS = G::RS, TS = G::TS;
+    using G = PassGeom<NKB>;
+    constexpr int SL = G::SL, TN = G::TN, NSEG = G::NSEG, RS = G::RS, TS = G::TS;
     const double* AL = TB; const double* CP = TB + TN; const double* PP = TB + 2 * TN; const double* QQ = TB + 3 * TN;
     constexpr bool RUNP = pass_runp<NKB>();
     const double* PI = TB + 4 * TN; const double* PSI = TB + 5 * TN;
@@ -287,7 +269,7 @@ __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const 
             prev = r - (u ? tal.y : tal.x) * prev;
             d[m] = prev;
         }
-        if (SL == 8 && mm == 2) __builtin_amdgcn_sched_barrier(0);
+        if (mm == 2) __builtin_amdgcn_sched_barrier(0);
     }
     // ---- forward carries: tot_j = E_j + P_j tot_{j-1} over the segments of the row, Kogge-Stone on the E part
     const double2 fm01 = *reinterpret_cast<const double2*>(AL + tb + SL);
@@ -322,7 +304,7 @@ __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const 
             nxt = dp - (u ? tcp.y : tcp.x) * nxt;
             d[m] = nxt;
         }
-        if (SL == 8 && mm == 4) __builtin_amdgcn_sched_barrier(0);
+        if (mm == 4) __builtin_amdgcn_sched_barrier(0);
     }
     // ---- backward carries: first_j = F_j + Q_j first_{j+1}
     const double2 bm01 = *reinterpret_cast<const double2*>(PP + tb + SL);
@@ -335,7 +317,7 @@ __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const 
     double sin_ = dpp0_f64<DPP_ROW_SHL(1)>(f);
     sin_ = s_last ? 0.0 : sin_;
     double* srow = Sp + tl * RS + kb;
-    const int sx = NKB == 2 ? (seg >> 2) & 3 : (SL == 8 ? (seg >> 1) & 3 : 0);
+    const int sx = NKB == 2 ? (seg >> 2) & 3 : (seg >> 1) & 3;
     if (RUNP) {      // PSI rebuilt as a running product of (-CP), back to front
         double psi = 1.0;
 #pragma unroll
@@ -362,13 +344,13 @@ __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const 
 // rule set of dense_strike_slopes_local[_var] (ivs_surface_dense[_var].hpp) re-cut for 8-knot segments.
 template <int NKB, bool VAR>
 __device__ __forceinline__ void pass_local_tables(const double* X, int n, int lane, double* TB) {
-    using G = PassGeom<NKB, 8>;
+    using G = PassGeom<NKB>;
 #pragma unroll
     for (int blk = 0; blk < NKB; ++blk) {
         const int k = blk * 64 + lane;
         double r0, r1, r2;
         local_tables_rt(X, n, k, r0, r1, r2);
-        const int kl = p_tix<8>(k);
+        const int kl = p_tix(k);
         TB[kl] = r0; TB[G::TN + kl] = r1; TB[2 * G::TN + kl] = r2;
     }
     __syncthreads();
@@ -376,7 +358,7 @@ __device__ __forceinline__ void pass_local_tables(const double* X, int n, int la
 // One pass: local slopes of the RP rows staged in Yp -> Sp.  Lane = (row of the pass, 8-knot segment).  No barrier inside.
 template <int METHOD, int NKB, bool VAR>
 __device__ __forceinline__ void pass_local_slopes(const double* Yp, double* Sp, const double* TB, int lane, int n) {
-    using G = PassGeom<NKB, 8>;
+    using G = PassGeom<NKB>;
     constexpr bool AK = METHOD == IVS_AKIMA;
     constexpr int TN = G::TN, NSEG = G::NSEG, RS = G::RS, TS = G::TS;
     const double* R0 = TB; const double* R1 = TB + TN; const double* R2 = TB + 2 * TN;
@@ -438,7 +420,7 @@ __device__ __forceinline__ void pass_local_slopes(const double* Yp, double* Sp, 
     double e_last = 0.0;
     if (!AK) {
         const int k1 = y_swz<NKB>(n - 1), k2 = y_swz<NKB>(n - 2), k3 = y_swz<NKB>(n - 3);
-        const int t1 = p_tix<8>(n - 1), t2 = p_tix<8>(n - 2), t3 = p_tix<8>(n - 3);
+        const int t1 = p_tix(n - 1), t2 = p_tix(n - 2), t3 = p_tix(n - 3);
         const double m2 = (yrow[k1] - yrow[k2]) * R0[t2], m3 = (yrow[k2] - yrow[k3]) * R0[t3];
         e_last = pchip_edge(m2, m3, R1[t1], R2[t1]);
     }
@@ -477,30 +459,22 @@ __device__ __forceinline__ void pass_local_slopes(const double* Yp, double* Sp, 
 __device__ unsigned long long* d_pass_ends = nullptr;
 #endif
 
-#ifndef IVS_PCHIP3
-#define IVS_PCHIP3 3      // bit 0: pchip NT16 <= 64 strikes at 3 wavefronts per SIMD (161 VGPRs, no scratch); bit 1: 65..128 strikes too (48 B scratch)
-#endif
-#ifndef IVS_AKIMA3
-#define IVS_AKIMA3 3      // the same for akima (164 / 166 VGPRs with the rolling maturity slopes, IVS_AKIMA_ROLL; 240 before)
-#endif
-__host__ __device__ constexpr bool pass_local_three(int method, int nkb, bool nt16) {
-    return nt16 && ((method == IVS_PCHIP && ((IVS_PCHIP3 >> (nkb - 1)) & 1)) || (method == IVS_AKIMA && ((IVS_AKIMA3 >> (nkb - 1)) & 1)));
-}
 // NT16 (VAR only): the batch has the full 16 maturities (BASELINE config 5): the run-time maturity count -- masked rows, the
 // third tap of the last system row, the select chain for the hold row -- compiles away (~60 VALU instructions per surface).
-template <int METHOD, int NKB, bool VAR, int SL = 8, bool TSH = true, bool NT16 = false>
-// Wavefronts per SIMD: 3 (168 VGPRs); the run-time-shape instantiations of pchip / akima need ~200 (the per-lane maturity
-// solve of the local rules) and run at 2 without scratch -- at 3 they spilled 14-36 registers and lost 3-30 %.
-__global__ __launch_bounds__(64, SL == 4 ? 4 : ((d_is_local(METHOD) && VAR && !pass_local_three(METHOD, NKB, NT16)) ? 2 : 3))
+template <int METHOD, int NKB, bool VAR, bool TSH = true, bool NT16 = false>
+// Wavefronts per SIMD: 3 (168 VGPRs); the run-time-maturity-count instantiations of pchip / akima need ~200 (the per-lane
+// maturity solve of the local rules) and run at 2 without scratch -- at 3 they spilled 14-36 registers and lost 3-30 %.
+// Their NT16 forms fit 3: pchip 161 VGPRs (48 B of scratch at 65..128 strikes), akima 164 / 166 with the rolling maturity slopes.
+__global__ __launch_bounds__(64, (d_is_local(METHOD) && VAR && !NT16) ? 2 : 3)
 void surface_pass_kernel(SurfaceParams p, VarList list) {
 #ifdef IVS_PASS_ENDSTAMP
     if (threadIdx.x == 0 && d_pass_ends) d_pass_ends[blockIdx.x * 2] = wall_clock64();
 #endif
     if (!VAR && p.mode && *((const int IVS_CONST*)p.mode)) return;      // "missing quotes first": the compaction kernel takes the batch
-    using G = PassGeom<NKB, SL>;
+    using G = PassGeom<NKB>;
     constexpr int RP = G::RP, NPASS = G::NPASS, KCAP = G::KCAP, RS = G::RS, TN = G::TN;
-    // passes in flight per lane (8-knot segments, 64 strikes: a whole surface; the local-slope methods need the registers: one pass)
-    constexpr int PFP = (NKB > 1 || d_is_local(METHOD)) ? 1 : (SL == 4 ? IVS_PASS_PFP4 : NPASS);
+    // passes in flight per lane (64 strikes: a whole surface; the local-slope methods need the registers: one pass)
+    constexpr int PFP = (NKB > 1 || d_is_local(METHOD)) ? 1 : NPASS;
     constexpr int PPL = RP * NKB;                    // doubles per lane and pass
     static_assert(NPASS % PFP == 0, "prefetch slots rotate with the passes");
     constexpr bool STEP = d_is_step(METHOD);                                   // nearest / zero / from_derivatives
@@ -508,7 +482,6 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
     constexpr bool LOCAL = d_is_local(METHOD);                                  // pchip / akima: three tables instead of six, no sweeps
     constexpr bool QUADK = d_is_quad(METHOD);                                   // quadratic B-spline: the not-a-knot machinery on another system
     static_assert(LERP || LOCAL || QUADK || METHOD == IVS_CUBIC || METHOD == IVS_CUBICSPLINE, "methods of the dense kernels");
-    static_assert(!LOCAL || SL == 8, "local slopes are cut for 8-knot segments");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const int mT = p.mT, mK = p.mK;
@@ -546,8 +519,8 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
     // ---- work distribution: work queues (WorkQueue, ivs_surface_generic.hpp)
     bool told = false;
     WorkQueue wq;
-    if (!VAR) wq.init(p.queue, p.map_groups, p.B, IVS_PASS_CHUNK, lane);
-    else wq.init(p.queue + list.qslot * 8 * QUEUE_STRIDE, 8, list.items ? (int64_t)*list.count : p.B, IVS_PASS_CHUNK, lane);
+    if (!VAR) wq.init(p.queue, p.map_groups, p.B, PASS_CHUNK, lane);
+    else wq.init(p.queue + list.qslot * 8 * QUEUE_STRIDE, 8, list.items ? (int64_t)*list.count : p.B, PASS_CHUNK, lane);
     auto at = [&](int64_t i, int& n, int64_t& koff) -> int64_t {
         if (VAR && list.items) { const VarItem v = list.items[i]; n = v.n; koff = v.koff; return v.b; }
         n = p.nK; koff = i * p.k_stride; return i;
@@ -566,22 +539,6 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
             }
         } else {
             const double* sb = p.k_off ? p.sigma + (int64_t)nT * ko : p.sigma + b * (int64_t)nT * p.nK;
-#if IVS_PASS_WIDE
-            // lane = (row of a row pair, strike pair): rows are nn doubles apart, so a pair is 8-byte aligned only (global
-            // loads take that); the last strike of an odd row is fetched alone -- its pair would reach into the next row,
-            // and behind the last row of the batch past the end of the caller's array
-            typedef double v2d_a8 __attribute__((ext_vector_type(2), aligned(8)));
-            constexpr int LPR = 32 * NKB;                        // lanes per row
-#pragma unroll
-            for (int c = 0; c < PPL / 2; ++c) {
-                const int t = ps * RP + (NKB == 1 ? 2 * c + (lane >> 5) : c), k = 2 * (lane & (LPR - 1));
-                const double* src = sb + (int64_t)t * nn + k;
-                double2 v = double2{0.0, 0.0};                   // rows beyond nT, strikes beyond n: zeros
-                if (t < nT && k + 1 < nn) { const v2d_a8 w = *reinterpret_cast<const v2d_a8*>(src); v.x = w.x; v.y = w.y; }
-                else if (t < nT && k < nn) v.x = *src;
-                pre[slot * PPL + 2 * c] = v.x; pre[slot * PPL + 2 * c + 1] = v.y;
-            }
-#else
 #pragma unroll
             for (int r = 0; r < RP; ++r)
 #pragma unroll
@@ -589,7 +546,6 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
                     const int t = ps * RP + r, k = blk * 64 + lane;
                     pre[(slot * RP + r) * NKB + blk] = (t < nT && k < nn) ? sb[(int64_t)t * nn + k] : 0.0;      // rows beyond nT: zeros
                 }
-#endif
         }
         if (ps == 0) {
 #pragma unroll
@@ -653,15 +609,6 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
 #pragma unroll
                 for (int c = 0; c < RP; ++c) acc = __builtin_fma(pre[slot * RP + c], 0.0, acc);
             } else {
-#if IVS_PASS_WIDE
-#pragma unroll
-                for (int c = 0; c < PPL / 2; ++c) {
-                    const int tl = NKB == 1 ? 2 * c + (lane >> 5) : c, k = 2 * (lane & (32 * NKB - 1));
-                    double2 v; v.x = pre[slot * PPL + 2 * c]; v.y = pre[slot * PPL + 2 * c + 1];
-                    *reinterpret_cast<double2*>(&Yp[tl * RS + y_swz<NKB>(k)]) = v;       // the slot swizzle keeps a pair together
-                    acc = __builtin_fma(v.x, 0.0, acc); acc = __builtin_fma(v.y, 0.0, acc);
-                }
-#else
 #pragma unroll
                 for (int r = 0; r < RP; ++r)
 #pragma unroll
@@ -670,7 +617,6 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
                         Yp[r * RS + y_swz<NKB>(blk * 64 + lane)] = v;
                         acc = __builtin_fma(v, 0.0, acc);
                     }
-#endif
             }
             if (ps == 0) {
                 bool same = tables_ok && n == n_prev;
@@ -694,7 +640,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
             if (ok) {
                 if (ps == 0 && !same_k) {
                     if (LOCAL) pass_local_tables<NKB, VAR>(Ksh, n, lane, TB);
-                    else if (!LERP && ABL != 1 && ABL != 6) pass_factor_tables<NKB, VAR, SL, QUADK>(Ksh, n, lane, TB, Sp + KCAP);
+                    else if (!LERP && ABL != 1 && ABL != 6) pass_factor_tables<NKB, VAR, QUADK>(Ksh, n, lane, TB, Sp + KCAP);
                 }
                 if (ps == 0 && !(same_k && kq_shared)) {
                     // ---- strike search + weights of this lane's output strike (once per strike grid / query grid)
@@ -725,7 +671,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
                         w3 = u * t * (t - 1.0);
                     }
                 }
-                const int o0 = y_swz<NKB>(jj), o1 = y_swz<NKB>(jj + 1), q0 = p_swz<SL, NKB>(jj), q1 = p_swz<SL, NKB>(jj + 1);
+                const int o0 = y_swz<NKB>(jj), o1 = y_swz<NKB>(jj + 1), q0 = p_swz<NKB>(jj), q1 = p_swz<NKB>(jj + 1);
                 if (LERP) {      // two gathers per row, RP in flight; the same arithmetic (and bits) as the one-pass kernel
                     double g0[RP], g1[RP];
 #pragma unroll
@@ -754,7 +700,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
                     continue;
                 }
                 if (LOCAL) pass_local_slopes<METHOD, NKB, VAR>(Yp, Sp, TB, lane, n);
-                else if (ABL != 1 && ABL != 6) pass_sweeps<NKB, VAR, SL, QUADK>(Yp, Sp, TB, lane, n);
+                else if (ABL != 1 && ABL != 6) pass_sweeps<NKB, VAR, QUADK>(Yp, Sp, TB, lane, n);
                 __syncthreads();
                 // ---- strike evaluation of the pass's rows (q-lane), gathers pipelined LA rows ahead
                 if (ABL == 2 || ABL == 6) {
@@ -766,8 +712,8 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
                 double g0[4], g1[4], g2[4], g3[4];
                 // operands of the four weights: (y_j, y_j+1, s_j, s_j+1), or for the quadratic spline the coefficients c[jj-1 .. jj+2]
                 const double* PA = QUADK ? Sp : Yp;
-                const int a0i = QUADK ? p_swz<SL, NKB>(jj > 0 ? jj - 1 : 0) : o0, a1i = QUADK ? q0 : o1;
-                const int b0i = QUADK ? q1 : q0, b1i = QUADK ? p_swz<SL, NKB>(jj + 2 < KCAP ? jj + 2 : KCAP - 1) : q1;
+                const int a0i = QUADK ? p_swz<NKB>(jj > 0 ? jj - 1 : 0) : o0, a1i = QUADK ? q0 : o1;
+                const int b0i = QUADK ? q1 : q0, b1i = QUADK ? p_swz<NKB>(jj + 2 < KCAP ? jj + 2 : KCAP - 1) : q1;
 #pragma unroll
                 for (int r = 0; r < LA; ++r) {
                     g0[r] = PA[r * RS + a0i]; g1[r] = PA[r * RS + a1i]; g2[r] = Sp[r * RS + b0i]; g3[r] = Sp[r * RS + b1i];
@@ -806,21 +752,13 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
 }
 
 // one launch; run-time-shape batches with the full 16 maturities take the NT16 instantiation
-template <int METHOD, int NKB, bool VAR, int SL>
+template <int METHOD, int NKB, bool VAR>
 inline void launch_pass_nt(bool nt16, int64_t grid, size_t lds, hipStream_t st, const SurfaceParams& p, const VarList& list) {
     if constexpr (VAR) {
-        if (nt16) { hipLaunchKernelGGL((surface_pass_kernel<METHOD, NKB, true, SL, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, list); return; }
+        if (nt16) { hipLaunchKernelGGL((surface_pass_kernel<METHOD, NKB, true, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, list); return; }
     }
-    hipLaunchKernelGGL((surface_pass_kernel<METHOD, NKB, VAR, SL, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, list);
+    hipLaunchKernelGGL((surface_pass_kernel<METHOD, NKB, VAR, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, list);
 }
-#ifndef IVS_AKIMA_FIXED
-#define IVS_AKIMA_FIXED 1      // 64 x 16 akima on the row-pass kernel (0: the one-pass kernel, rounds 1-2)
-#endif
-template <int NKB, bool VAR>
-inline void launch_pass_akima(bool nt16, int64_t grid, size_t lds, hipStream_t st, const SurfaceParams& p, const VarList& list) {
-    if constexpr (VAR || (IVS_AKIMA_FIXED && NKB == 1)) launch_pass_nt<IVS_AKIMA, NKB, VAR, 8>(nt16, grid, lds, st, p, list);
-}
-
 // Dispatch of the row-pass kernels.  Returns 1 if dispatched (pass kernel(s) + filtered generic redo pass), 0 if the
 // call is outside their scope (see the head of this file), -1 on a launch error.
 inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, const char** name) {
@@ -836,11 +774,7 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
     if (!p.k_off && p.k_stride != 0 && p.k_stride < p.nK) return 0;
     if (p.k_off && p.B > 0x7fffffffLL) return 0;
     const bool fixed64 = !p.k_off && p.nK == DK && p.nT == DT && !(reinterpret_cast<uintptr_t>(p.sigma) & 15);
-#ifndef IVS_PASS_NT16
-#define IVS_PASS_NT16 1      // 0: A/B builds without the NT16 instantiations
-#endif
-    const bool nt16 = IVS_PASS_NT16 && p.nT == DT;       // run-time-shape kernels: maturity count fixed at compile time (NT16)
-    if (!IVS_AKIMA_FIXED && fixed64 && p.method == IVS_AKIMA) return 0;      // rounds 1-2: 64 x 16 akima stayed on the one-pass kernel (at 168 VGPRs the row-pass form spilled 50 registers; see IVS_AKIMA_ROLL)
+    const bool nt16 = p.nT == DT;       // run-time-shape kernels: maturity count fixed at compile time (NT16)
     TqShared* tq = reinterpret_cast<TqShared*>(cx.ws);
     if (tsh) {
         if (fixed64 || nt16) launch_tq_tables<false>(p, tq, st); else launch_tq_tables<true>(p, tq, st);      // 16 maturities: the fixed-count tables
@@ -855,7 +789,7 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
     p.queue = tq->queue;
     auto grid_for = [&](size_t lds, int64_t work, int wg_cap = 12) {
         int per_cu = (int)((160 * 1024) / (((lds + 1279) / 1280) * 1280));     // LDS is granted in 1280-byte granules
-        per_cu = per_cu > wg_cap ? wg_cap : (per_cu < 1 ? 1 : per_cu);         // 3 wavefronts per SIMD (168 VGPRs); 4 with 4-knot segments (128)
+        per_cu = per_cu > wg_cap ? wg_cap : (per_cu < 1 ? 1 : per_cu);         // 3 wavefronts per SIMD (168 VGPRs)
 #ifdef IVS_PASS_PER_CU
         per_cu = IVS_PASS_PER_CU;                                              // diagnostic builds (tools/pass_api.hip)
 #endif
@@ -878,42 +812,41 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
         case IVS_QUADRATIC: mi = 9; break;
         default: mi = 8; break;
     }
-    // one launch of surface_pass_kernel<method, NKB, VAR, SL> over `list`; the lerp methods carry no S plane and no tables
+    // one launch of surface_pass_kernel<method, NKB, VAR> over `list`; the lerp methods carry no S plane and no tables
 #ifdef IVS_DIAG_MINIMAL
-#define IVS_PASS_LAUNCH(NKB_, VAR_, SL_, CAP, LIST)                                                                                      \
+#define IVS_PASS_LAUNCH(NKB_, VAR_, CAP, LIST)                                                                                           \
     {                                                                                                                                    \
-        const size_t lds = pass_lds_bytes<NKB_, VAR_, SL_, 0>();                                                                         \
+        const size_t lds = pass_lds_bytes<NKB_, 0>();                                                                                    \
         const int64_t grid = grid_for(lds, p.B, CAP);                                                                                    \
         if (!(VAR_)) p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);                                                          \
-        hipLaunchKernelGGL((surface_pass_kernel<IVS_CUBIC, NKB_, VAR_, SL_>), dim3((unsigned)grid), dim3(64), lds, st, p, LIST);         \
+        hipLaunchKernelGGL((surface_pass_kernel<IVS_CUBIC, NKB_, VAR_>), dim3((unsigned)grid), dim3(64), lds, st, p, LIST);              \
     }
 #else
-#define IVS_PASS_LAUNCH(NKB_, VAR_, SL_, CAP, LIST)                                                                                      \
+#define IVS_PASS_LAUNCH(NKB_, VAR_, CAP, LIST)                                                                                           \
     {                                                                                                                                    \
-        size_t lds = lerp ? pass_lds_bytes<NKB_, VAR_, SL_, 1>() : (local ? pass_lds_bytes<NKB_, VAR_, SL_, 2>() : pass_lds_bytes<NKB_, VAR_, SL_, 0>());  \
+        size_t lds = lerp ? pass_lds_bytes<NKB_, 1>() : (local ? pass_lds_bytes<NKB_, 2>() : pass_lds_bytes<NKB_, 0>());                 \
         if (!tsh) lds += PASS_TQ_DOUBLES * 8;                                                                                            \
-        const int64_t grid = grid_for(lds, p.B, (local && (VAR_) && !pass_local_three(p.method, NKB_, nt16)) ? 8 : (CAP));               \
+        const int64_t grid = grid_for(lds, p.B, (local && (VAR_) && !nt16) ? 8 : (CAP));      /* 2 wavefronts per SIMD */                \
         if (!(VAR_)) p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);                                                          \
         if (!tsh) {                                                                                                                      \
-            hipLaunchKernelGGL((surface_pass_kernel<IVS_LINEAR, NKB_, VAR_, 8, false>), dim3((unsigned)grid), dim3(64), lds, st, p, LIST);                              \
+            hipLaunchKernelGGL((surface_pass_kernel<IVS_LINEAR, NKB_, VAR_, false>), dim3((unsigned)grid), dim3(64), lds, st, p, LIST);  \
         } else                                                                                                                           \
         switch (p.method) {                                                                                                              \
-            case IVS_CUBIC: launch_pass_nt<IVS_CUBIC, NKB_, VAR_, SL_>(nt16, grid, lds, st, p, LIST); break;             \
-            case IVS_CUBICSPLINE: launch_pass_nt<IVS_CUBICSPLINE, NKB_, VAR_, SL_>(nt16, grid, lds, st, p, LIST); break; \
-            case IVS_LINEAR: launch_pass_nt<IVS_LINEAR, NKB_, VAR_, SL_>(nt16, grid, lds, st, p, LIST); break;           \
-            case IVS_NEAREST: launch_pass_nt<IVS_NEAREST, NKB_, VAR_, SL_>(nt16, grid, lds, st, p, LIST); break;         \
-            case IVS_ZERO: launch_pass_nt<IVS_ZERO, NKB_, VAR_, SL_>(nt16, grid, lds, st, p, LIST); break;               \
-            case IVS_FROM_DERIVATIVES: launch_pass_nt<IVS_FROM_DERIVATIVES, NKB_, VAR_, SL_>(nt16, grid, lds, st, p, LIST); break; \
-            case IVS_QUADRATIC: launch_pass_nt<IVS_QUADRATIC, NKB_, VAR_, 8>(nt16, grid, lds, st, p, LIST); break;       \
-            case IVS_PCHIP: launch_pass_nt<IVS_PCHIP, NKB_, VAR_, 8>(nt16, grid, lds, st, p, LIST); break;               \
-            case IVS_AKIMA: launch_pass_akima<NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                                \
-            default: launch_pass_nt<IVS_SLINEAR, NKB_, VAR_, SL_>(nt16, grid, lds, st, p, LIST); break;                  \
+            case IVS_CUBIC: launch_pass_nt<IVS_CUBIC, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                  \
+            case IVS_CUBICSPLINE: launch_pass_nt<IVS_CUBICSPLINE, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                      \
+            case IVS_LINEAR: launch_pass_nt<IVS_LINEAR, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                \
+            case IVS_NEAREST: launch_pass_nt<IVS_NEAREST, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                              \
+            case IVS_ZERO: launch_pass_nt<IVS_ZERO, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                    \
+            case IVS_FROM_DERIVATIVES: launch_pass_nt<IVS_FROM_DERIVATIVES, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;            \
+            case IVS_QUADRATIC: launch_pass_nt<IVS_QUADRATIC, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                          \
+            case IVS_PCHIP: launch_pass_nt<IVS_PCHIP, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                  \
+            case IVS_AKIMA: launch_pass_nt<IVS_AKIMA, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                  \
+            default: launch_pass_nt<IVS_SLINEAR, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                       \
         }                                                                                                                                \
     }
 #endif
     if (fixed64) {
-        constexpr int FSL = IVS_PASS_SL;
-        IVS_PASS_LAUNCH(1, false, FSL, (FSL == 4 ? 16 : 12), none)
+        IVS_PASS_LAUNCH(1, false, 12, none)
         *name = names[0][mi];
     } else {
         VarItem* lists = nullptr;
@@ -929,8 +862,8 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
         }
         const VarList wl1{lists, counts, 0}, wl2{lists ? lists + p.B : nullptr, counts ? counts + 1 : nullptr, 1};
         const bool need1 = p.k_off ? true : p.nK <= 64, need2 = p.nK > 64;
-        if (need1) IVS_PASS_LAUNCH(1, true, 8, 12, wl1)
-        if (need2) IVS_PASS_LAUNCH(2, true, 8, IVS_PASS_CAP2, wl2)
+        if (need1) IVS_PASS_LAUNCH(1, true, 12, wl1)
+        if (need2) IVS_PASS_LAUNCH(2, true, PASS_CAP2, wl2)
         *name = names[1][mi];
     }
 #undef IVS_PASS_LAUNCH

@@ -238,7 +238,8 @@ def test_nan_masked_quotes_vs_oracle(method):
 
 @pytest.mark.parametrize("method", DENSE_METHODS)
 def test_masked_rows_with_few_quotes_and_infinities(method):
-    """The compaction kernel behind the dense kernels (ivs_surface_masked.hpp): rows thinned down to 2..7 quotes (pchip's
+    """The compaction kernels behind the dense kernels (ivs_surface_masked.hpp: linear, slinear, nearest, zero,
+    from_derivatives; ivs_surface_masked_pass.hpp: the methods with slopes): rows thinned down to 2..7 quotes (pchip's
     two-knot rule, akima's three, the not-a-knot minimum of four), quotes missing at the row ends, sparse NaN, and an
     infinity, which is a VALUE (it propagates like in the oracle), not a missing quote."""
     from iv_interpolation_amd import synth
