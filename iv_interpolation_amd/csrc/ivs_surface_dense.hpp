@@ -1282,6 +1282,26 @@ inline int dense_map_groups(int64_t grid, int64_t B, int forced) {
     return r < 1 ? 1 : r;
 }
 
+// Maturity tables and queue heads of a call, shared by the surface launchers.  Shared T / Tq: the batch-wide tables go
+// into the workspace on the same stream (NTR: run-time maturity count; the table kernel also zeroes the queue heads);
+// per-surface maturities: no table kernel runs, the queue heads are zeroed here.  Returns false on a stream error.
+template <bool NTR>
+inline bool launch_tq_or_zero_queue(SurfaceParams& p, const LaunchCtx& cx, bool tsh, bool set_mode) {
+    TqShared* tq = reinterpret_cast<TqShared*>(cx.ws);
+    if (tsh) {
+        launch_tq_tables<NTR>(p, tq, cx.st);
+        p.tqs = tq;
+        p.redo = tq->redo;
+        p.mode = set_mode ? &tq->mode : nullptr;
+    } else {
+        if (hipMemsetAsync(tq->queue, 0, sizeof(TqShared::queue), cx.st) != hipSuccess) return false;
+        p.tqs = nullptr;
+        p.redo = nullptr;
+    }
+    p.queue = tq->queue;
+    return true;
+}
+
 #ifndef IVS_DIAG_MINIMAL      // diagnostic builds (tools/pass_api.hip) skip the launchers that instantiate every kernel
 inline bool launch_surface_masked(const SurfaceParams& p, const LaunchCtx& cx);      // ivs_surface_masked.hpp
 // Dense dispatch.  Returns 1 if dispatched (dense kernel + filtered generic redo pass), 0 if the
@@ -1304,16 +1324,7 @@ inline int launch_surface_dense(const SurfaceParams& p_in, const LaunchCtx& cx, 
     p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);
     const bool tsh = p.t_stride == 0 && p.tq_stride == 0;
     const bool wl = p.mT <= D_WLDS_MAX_MT;
-    if (tsh) {                                   // batch-wide maturity tables into the workspace, same stream
-        TqShared* tq = reinterpret_cast<TqShared*>(cx.ws);
-        launch_tq_tables<false>(p, tq, st);
-        p.tqs = tq;
-        p.redo = tq->redo;
-        p.mode = &tq->mode;
-    } else {                                     // per-surface maturities: no table kernel runs, the queue heads are zeroed here
-        if (hipMemsetAsync(reinterpret_cast<TqShared*>(cx.ws)->queue, 0, sizeof(TqShared::queue), st) != hipSuccess) return -1;
-    }
-    p.queue = reinterpret_cast<TqShared*>(cx.ws)->queue;
+    if (!launch_tq_or_zero_queue<false>(p, cx, tsh, true)) return -1;
     if (p.map_groups > 16) p.map_groups = 16;
     if (dbg) {   // diagnostic build: cubic and linear, shared T only
         if (!tsh) return 0;

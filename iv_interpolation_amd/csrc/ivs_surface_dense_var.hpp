@@ -589,4 +589,27 @@ __global__ __launch_bounds__(64, 2) void surface_dense_var_kernel(SurfaceParams 
     }
 }
 
+// ---- host side shared by the launchers of the variable-shape kernels (one-pass and row-pass)
+// Work lists of a call.  Ragged batch: classified once into one list per size class (workspace: counters, then
+// V_NCLASS x B items); uniform batch: the empty lists.  need1 / need2: the size classes the call has to launch.
+struct VarWork { VarList wl1, wl2; bool need1, need2; };
+inline bool var_work_lists(const SurfaceParams& p, const LaunchCtx& cx, VarWork& w) {
+    VarItem* lists = nullptr;
+    int32_t* counts = nullptr;
+    if (p.k_off) {
+        counts = reinterpret_cast<int32_t*>(cx.ws + WS_TQ_BYTES);
+        lists = reinterpret_cast<VarItem*>(cx.ws + WS_TQ_BYTES + WS_COUNTS_BYTES);
+        if (hipMemsetAsync(counts, 0, WS_COUNTS_BYTES, cx.st) != hipSuccess) return false;
+        int64_t cb = (p.B + 1023) / 1024;
+        const int64_t cap = (int64_t)cx.num_cu * 8;
+        if (cb > cap) cb = cap;
+        hipLaunchKernelGGL(var_classify_kernel, dim3((unsigned)cb), dim3(256), 0, cx.st, p, lists, lists + p.B, counts);
+    }
+    w.wl1 = VarList{lists, counts, 0};
+    w.wl2 = VarList{lists ? lists + p.B : nullptr, counts ? counts + 1 : nullptr, 1};
+    w.need1 = p.k_off ? true : p.nK <= 64;
+    w.need2 = p.nK > 64;
+    return true;
+}
+
 }  // namespace ivs

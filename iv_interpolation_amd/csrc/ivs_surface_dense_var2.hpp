@@ -470,31 +470,10 @@ inline int launch_surface_dense_var(const SurfaceParams& p_in, const LaunchCtx& 
     if (generic_lds_bytes(p.nK, p.nT) > 160 * 1024) return 0;
     if (!(d_is_hermite(p.method) || p.method == IVS_LINEAR || p.method == IVS_SLINEAR)) return 0;
     const bool wl = p.mT <= D_WLDS_MAX_MT;
-    const bool need1 = p.k_off ? true : p.nK <= 64;
-    const bool need2 = p.nK > 64;
-    if (tsh) {
-        TqShared* tq = reinterpret_cast<TqShared*>(cx.ws);
-        launch_tq_tables<true>(p, tq, st);
-        p.tqs = tq;
-        p.redo = tq->redo;
-    } else {                                     // per-surface maturities: no table kernel runs, the queue heads are zeroed here
-        if (hipMemsetAsync(reinterpret_cast<TqShared*>(cx.ws)->queue, 0, sizeof(TqShared::queue), st) != hipSuccess) return -1;
-    }
-    p.queue = reinterpret_cast<TqShared*>(cx.ws)->queue;
-    // ragged batch: classify once into one work list per size class (workspace: counters, then V_NCLASS x B items)
-    VarItem* lists = nullptr;
-    int32_t* counts = nullptr;
-    if (p.k_off) {
-        if (p.B > 0x7fffffffLL) return 0;
-        counts = reinterpret_cast<int32_t*>(cx.ws + WS_TQ_BYTES);
-        lists = reinterpret_cast<VarItem*>(cx.ws + WS_TQ_BYTES + WS_COUNTS_BYTES);
-        if (hipMemsetAsync(counts, 0, WS_COUNTS_BYTES, st) != hipSuccess) return -1;
-        int64_t cb = (p.B + 1023) / 1024;
-        const int64_t cap = (int64_t)cx.num_cu * 8;
-        if (cb > cap) cb = cap;
-        hipLaunchKernelGGL(var_classify_kernel, dim3((unsigned)cb), dim3(256), 0, st, p, lists, lists + p.B, counts);
-    }
-    const VarList wl1{lists, counts, 0}, wl2{lists ? lists + p.B : nullptr, counts ? counts + 1 : nullptr, 1};
+    if (!launch_tq_or_zero_queue<true>(p, cx, tsh, false)) return -1;
+    if (p.k_off && p.B > 0x7fffffffLL) return 0;
+    VarWork vw;
+    if (!var_work_lists(p, cx, vw)) return -1;
     auto grid_for = [&](size_t lds) {
         int per_cu = (int)((160 * 1024) / lds);
         per_cu = per_cu > 8 ? 8 : (per_cu < 1 ? 1 : per_cu);
@@ -505,24 +484,24 @@ inline int launch_surface_dense_var(const SurfaceParams& p_in, const LaunchCtx& 
     {                                                                                                                \
         const size_t lds = dense_var_lds_bytes<1>(p.mT);                                                             \
         const int64_t grid = grid_for(lds);                                                                          \
-        if (wl && tsh) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, wl1);    \
-        else if (tsh) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, false, true>), dim3((unsigned)grid), dim3(64), lds, st, p, wl1);    \
-        else if (wl) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, wl1);     \
-        else hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, false, false>), dim3((unsigned)grid), dim3(64), lds, st, p, wl1);            \
+        if (wl && tsh) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);    \
+        else if (tsh) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, false, true>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);    \
+        else if (wl) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);     \
+        else hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, false, false>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);            \
     }
 #define IVS_VAR_LAUNCH2(M)                                                                                           \
     {                                                                                                                \
         const size_t lds = dense_var2_lds_bytes(p.mT);          /* 40 KB: below the 64 KiB default limit */          \
         const int64_t grid = grid_for(lds);                                                                          \
-        if (wl && tsh) hipLaunchKernelGGL((surface_dense_var2_kernel<M, true, true>), dim3((unsigned)grid), dim3(128), lds, st, p, wl2);     \
-        else if (tsh) hipLaunchKernelGGL((surface_dense_var2_kernel<M, false, true>), dim3((unsigned)grid), dim3(128), lds, st, p, wl2);     \
-        else if (wl) hipLaunchKernelGGL((surface_dense_var2_kernel<M, true, false>), dim3((unsigned)grid), dim3(128), lds, st, p, wl2);      \
-        else hipLaunchKernelGGL((surface_dense_var2_kernel<M, false, false>), dim3((unsigned)grid), dim3(128), lds, st, p, wl2);             \
+        if (wl && tsh) hipLaunchKernelGGL((surface_dense_var2_kernel<M, true, true>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);     \
+        else if (tsh) hipLaunchKernelGGL((surface_dense_var2_kernel<M, false, true>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);     \
+        else if (wl) hipLaunchKernelGGL((surface_dense_var2_kernel<M, true, false>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);      \
+        else hipLaunchKernelGGL((surface_dense_var2_kernel<M, false, false>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);             \
     }
 #define IVS_VAR_CASE(M, NAME)                                                  \
     case M:                                                                    \
-        if (need1) IVS_VAR_LAUNCH1(M)                                          \
-        if (need2) IVS_VAR_LAUNCH2(M)                                          \
+        if (vw.need1) IVS_VAR_LAUNCH1(M)                                        \
+        if (vw.need2) IVS_VAR_LAUNCH2(M)                                        \
         *name = NAME;                                                          \
         break;
     bool known = true;

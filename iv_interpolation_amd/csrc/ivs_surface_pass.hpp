@@ -775,18 +775,8 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
     if (p.k_off && p.B > 0x7fffffffLL) return 0;
     const bool fixed64 = !p.k_off && p.nK == DK && p.nT == DT && !(reinterpret_cast<uintptr_t>(p.sigma) & 15);
     const bool nt16 = p.nT == DT;       // run-time-shape kernels: maturity count fixed at compile time (NT16)
-    TqShared* tq = reinterpret_cast<TqShared*>(cx.ws);
-    if (tsh) {
-        if (fixed64 || nt16) launch_tq_tables<false>(p, tq, st); else launch_tq_tables<true>(p, tq, st);      // 16 maturities: the fixed-count tables
-        p.tqs = tq;
-        p.redo = tq->redo;
-        p.mode = fixed64 ? &tq->mode : nullptr;
-    } else {      // per-surface maturities: the T-phase runs inside the kernel; only the queue heads need zeroing
-        if (hipMemsetAsync(tq->queue, 0, sizeof(TqShared::queue), st) != hipSuccess) return -1;
-        p.tqs = nullptr;
-        p.redo = nullptr;
-    }
-    p.queue = tq->queue;
+    if (!(fixed64 || nt16 ? launch_tq_or_zero_queue<false>(p, cx, tsh, fixed64)      // 16 maturities: the fixed-count tables
+                          : launch_tq_or_zero_queue<true>(p, cx, tsh, fixed64))) return -1;
     auto grid_for = [&](size_t lds, int64_t work, int wg_cap = 12) {
         int per_cu = (int)((160 * 1024) / (((lds + 1279) / 1280) * 1280));     // LDS is granted in 1280-byte granules
         per_cu = per_cu > wg_cap ? wg_cap : (per_cu < 1 ? 1 : per_cu);         // 3 wavefronts per SIMD (168 VGPRs)
@@ -849,21 +839,10 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
         IVS_PASS_LAUNCH(1, false, 12, none)
         *name = names[0][mi];
     } else {
-        VarItem* lists = nullptr;
-        int32_t* counts = nullptr;
-        if (p.k_off) {      // classify once into one work list per size class (workspace: counters, then B items per class)
-            counts = reinterpret_cast<int32_t*>(cx.ws + WS_TQ_BYTES);
-            lists = reinterpret_cast<VarItem*>(cx.ws + WS_TQ_BYTES + WS_COUNTS_BYTES);
-            if (hipMemsetAsync(counts, 0, WS_COUNTS_BYTES, st) != hipSuccess) return -1;
-            int64_t cb = (p.B + 1023) / 1024;
-            const int64_t cap = (int64_t)cx.num_cu * 8;
-            if (cb > cap) cb = cap;
-            hipLaunchKernelGGL(var_classify_kernel, dim3((unsigned)cb), dim3(256), 0, st, p, lists, lists + p.B, counts);
-        }
-        const VarList wl1{lists, counts, 0}, wl2{lists ? lists + p.B : nullptr, counts ? counts + 1 : nullptr, 1};
-        const bool need1 = p.k_off ? true : p.nK <= 64, need2 = p.nK > 64;
-        if (need1) IVS_PASS_LAUNCH(1, true, 12, wl1)
-        if (need2) IVS_PASS_LAUNCH(2, true, PASS_CAP2, wl2)
+        VarWork vw;
+        if (!var_work_lists(p, cx, vw)) return -1;
+        if (vw.need1) IVS_PASS_LAUNCH(1, true, 12, vw.wl1)
+        if (vw.need2) IVS_PASS_LAUNCH(2, true, PASS_CAP2, vw.wl2)
         *name = names[1][mi];
     }
 #undef IVS_PASS_LAUNCH
