@@ -27,6 +27,7 @@ from iv_interpolation_amd.frame_store import FrameStore, synthetic_symbol   # no
 MINUTE_TABLE = "minute_candles"
 CANDLE_TABLE = "reconstructed_candles"
 SURFACE_TABLE = "iv_surfaces"
+SMILE_TABLE = "iv_smiles"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -184,6 +185,11 @@ class CompleteOptimizedPipeline:
         return {"success": ok > 0, "batch_id": batch_id, "symbols_processed": ok, "total_input": total_in,
                 "total_output": total_out, "duration": duration}
 
+    def _interpolated_frames(self) -> list:
+        """The non-empty frames of interpolated_trading_tickers, in symbol order (input of the surface and smile tasks)."""
+        symbols = self.store.symbols("interpolated_trading_tickers")
+        return [f for f in (self.store.read_output(s) for s in symbols) if f is not None and not f.empty]
+
     def run_surfaces(self) -> dict:
         """Per-minute IV surface snapshots: every symbol of interpolated_trading_tickers is pivoted
         into one (expiry x strike) grid per underlying and minute, each grid goes through the surface engine, and one
@@ -191,8 +197,7 @@ class CompleteOptimizedPipeline:
         from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder
         print("\nSURFACES: PER-MINUTE IV SURFACE SNAPSHOTS (MI355X engine)")
         print("-" * 40)
-        symbols = self.store.symbols("interpolated_trading_tickers")
-        frames = [f for f in (self.store.read_output(s) for s in symbols) if f is not None and not f.empty]
+        frames = self._interpolated_frames()
         if not frames:
             return {"success": False, "error": "No interpolated data found for surfaces"}
         start = time.time()
@@ -210,6 +215,29 @@ class CompleteOptimizedPipeline:
         print(f"\nSURFACES COMPLETE: {duration:.1f}s, underlyings {len(results)}, snapshots {n_snap:,}, skipped symbols {skipped}")
         return {"success": n_snap > 0, "underlyings": len(results), "snapshots": n_snap, "skipped_symbols": skipped,
                 "duration": duration}
+
+    def run_smiles(self) -> dict:
+        """Delta-quoted smile summary: the snapshots of run_surfaces, then the ATM / 25-delta /
+        10-delta points of every tenor on the device, and one `iv_smiles` table per underlying (rule D7: columns
+        underlying, date, spot, tenor, atm, rr_10, bf_10, rr_25, bf_25)."""
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, smile_summary
+        print("\nSMILES: DELTA-QUOTED SMILE POINTS (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for smiles"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = 0
+        for res, q in zip(results, builder.smiles(results)):
+            table = smile_summary([q], [res])
+            self.store.write_table(SMILE_TABLE, res.underlying, table)
+            n_rows += len(table)
+            print(f"  {res.underlying}: {int(table['date'].nunique())} snapshots x {len(res.tenors)} tenors")
+        duration = time.time() - start
+        print(f"\nSMILES COMPLETE: {duration:.1f}s, underlyings {len(results)}, rows {n_rows:,}")
+        return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "duration": duration}
 
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
@@ -244,7 +272,7 @@ class CompleteOptimizedPipeline:
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -281,6 +309,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_data_bridge(symbols)
             elif args.task == "surfaces":
                 result = pipeline.run_surfaces()
+            elif args.task == "smiles":
+                result = pipeline.run_smiles()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define IVS_ABI_VERSION 4
+#define IVS_ABI_VERSION 5
 
 /* interpolation methods: the pandas method names that core.py:61 forwards
  * (`merged[col].interpolate(method=self.method)`) and that this engine implements */
@@ -268,6 +268,47 @@ typedef struct ivs_snapshot_args {
 int ivs_snapshot_assemble_f64(const ivs_snapshot_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Delta-quoted smile points off snapshot surfaces (ABI 5; DESIGN.md section 9, rules D1-D7): the at-the-money and the
+ * 25- / 10-delta call and put vols a desk quotes, read off the `out` of ivs_surface_batch_f64 on the device.  For every
+ * row (b, j) and every target the kernel inverts Black-Scholes call delta -> (strike, vol) on the chord between the first
+ * pair of neighbouring valid nodes that brackets the target:
+ *
+ *   vol [B][mT][mK]                    the surfaces (out of ivs_surface_batch_f64); a node with a non-finite or <= 0 vol or
+ *                                      strike is skipped (its neighbours pair up across it)
+ *   Kq, kq_stride / Tq, tq_stride      strike and tenor grids of snapshot b at Kq + b*kq_stride / Tq + b*tq_stride
+ *                                      (0 = one shared grid), mK / mT points, strikes ascending
+ *   spot [B], rate                     S of snapshot b and the scalar interest rate of d1 (0.0 = the schema default);
+ *                                      d1 is ivs_bs_greeks_f64's: (log(S/K) + (r + sigma^2/2) T) / (sigma sqrt(T))
+ *   z [nD] (HOST)                      targets as z = inv_cdf(call delta) (a put delta d means the call delta 1 + d; ATM
+ *                                      = 0.5 -> z = 0); 1 <= nD <= 16; copied into the kernel arguments by the call
+ *   q_vol, q_strike [B][mT][nD]        vol and strike where d1 - z changes sign, by 52 bisection steps on the chord
+ *   q_flags [B][mT][nD] (int32)        IVS_SM_*: NO_CROSSING and DEAD leave NaN in q_vol / q_strike; AMBIGUOUS = more than
+ *                                      one bracket, the lowest-strike one was used; DEAD = spot[b] or the tenor is not a
+ *                                      finite positive number or the row has fewer than 2 valid nodes
+ * Every output element is written, bitwise deterministically (plain stores, no atomics), in ONE launch.  mK >= 2 and
+ * B*mT < 2^31 are checked (IVS_ERANGE); B == 0 or mT == 0 is a no-op.  No workspace.
+ * rows_per_wave: how many consecutive rows one wavefront takes (their rows x nD inversions share its 64 lanes); 0 lets the
+ * call choose by batch size, 1..64/nD forces it (IVS_ERANGE outside).  The results do not depend on it, bit for bit.
+ */
+enum {
+    IVS_SM_OK          = 0,
+    IVS_SM_NO_CROSSING = 1,
+    IVS_SM_AMBIGUOUS   = 2,
+    IVS_SM_DEAD        = 4
+};
+typedef struct ivs_smile_args {
+    const double* vol;
+    const double* Kq; int64_t kq_stride;
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* z; /* host */
+    int32_t mK, mT, nD; int64_t B;
+    double* q_vol; double* q_strike; int32_t* q_flags;
+    int32_t rows_per_wave; /* 0 = chosen by the call; 1..64/nD = tuning / testing override, same results */
+} ivs_smile_args;
+int ivs_smile_delta_points_f64(const ivs_smile_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -314,7 +355,8 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
                                const uint32_t* words, int64_t n_words, double* out, uint8_t* valid, int64_t* rng_tail,
                                void* workspace, size_t workspace_bytes, void* stream);
 
-/* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 call on this thread dispatched to (host string) */
+/* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 call on this
+ * thread dispatched to (host string) */
 const char* ivs_last_kernel(void);
 
 /*

@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libivs.so")
 
 LINEAR, CUBIC, CUBICSPLINE, SLINEAR = 0, 1, 2, 3
 ST_OK, ST_TOO_FEW_KNOTS, ST_BAD_SHAPE, ST_ILL_CONDITIONED = 0, 1, 2, 4
+SM_OK, SM_NO_CROSSING, SM_AMBIGUOUS, SM_DEAD = 0, 1, 2, 4      # IVS_SM_*: per-target flags of the smile points
+SM_MAX_TARGETS = 16
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -21,7 +23,7 @@ def flag_map_groups(n: int) -> int:
     """IVS_FLAG_MAP_GROUPS(n): tuning override of the 64x16 kernel's surface -> workgroup mapping (0 = default)."""
     return (int(n) & 0xff) << 8
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # pandas method names (reference core.py:61 forwards self.method) -> engine codes
 NEAREST, ZERO, PCHIP, AKIMA, FROM_DERIVATIVES = 4, 5, 6, 7, 8
@@ -86,6 +88,14 @@ class SnapshotArgs(C.Structure):
                 ("sigma", _p), ("T", _p), ("spot", _p), ("quotes", _p), ("Kq", _p)]
 
 
+class SmileArgs(C.Structure):
+    """ivs_smile_args of include/ivs.h (field for field)."""
+    _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
+                ("spot", _p), ("rate", C.c_double), ("z", C.POINTER(C.c_double)),
+                ("mK", _i32), ("mT", _i32), ("nD", _i32), ("B", _i64),
+                ("q_vol", _p), ("q_strike", _p), ("q_flags", _p), ("rows_per_wave", _i32)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -115,6 +125,7 @@ SIGNATURES = {
     "ivs_debug_mode_offset": (_i64, []),
     "ivs_surface_workspace_bytes": (_sz, [_i64, _i32]),
     "ivs_snapshot_assemble_f64": (C.c_int, [C.POINTER(SnapshotArgs), _p, _sz, _p]),
+    "ivs_smile_delta_points_f64": (C.c_int, [C.POINTER(SmileArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }

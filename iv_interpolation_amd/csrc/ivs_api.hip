@@ -12,6 +12,7 @@
 #include "ivs_candles.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
+#include "ivs_smile.hpp"
 #include "ivs_snapshot.hpp"
 #include "ivs_surface_dense.hpp"
 #include "ivs_surface_dense_var2.hpp"
@@ -362,6 +363,44 @@ int ivs_snapshot_assemble_f64(const ivs_snapshot_args* a, void* workspace, size_
                        static_cast<hipStream_t>(stream), p);
     g_last_kernel = "snapshot_assemble_kernel";
     return check_launch("snapshot_assemble_kernel");
+}
+
+int ivs_smile_delta_points_f64(const ivs_smile_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_smile_delta_points_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->nD < 1 || a->nD > ivs::SM_MAX_D) return fail(IVS_ERANGE, "%s: nD=%d outside [1,%d]", fn, a->nD, ivs::SM_MAX_D);
+    if (a->mK < 2) return fail(IVS_ERANGE, "%s: mK=%d < 2: a bracket needs two nodes", fn, a->mK);
+    if (a->rows_per_wave < 0 || a->rows_per_wave > 64 / a->nD)
+        return fail(IVS_ERANGE, "%s: rows_per_wave=%d outside [0,%d] for nD=%d", fn, a->rows_per_wave, 64 / a->nD, a->nD);
+    if (a->B == 0 || a->mT == 0) return IVS_OK;
+    if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->z || !a->q_vol || !a->q_strike || !a->q_flags)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if ((a->kq_stride != 0 && a->kq_stride < a->mK) || (a->tq_stride != 0 && a->tq_stride < a->mT))
+        return fail(IVS_EINVAL, "%s: grid stride smaller than the grid", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    ivs::SmileParams p{};
+    p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
+    p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate;
+    for (int t = 0; t < a->nD; ++t) p.z[t] = a->z[t];
+    p.mK = a->mK; p.mT = a->mT; p.nD = a->nD; p.rows = a->B * a->mT;
+    p.q_vol = a->q_vol; p.q_strike = a->q_strike; p.q_flags = a->q_flags;
+    // rows per wavefront: fill the 64 lanes of the inversion phase, but keep ~16 wavefronts per CU while the batch is small
+    int dev, cus;
+    current_device(dev, cus);
+    int64_t group = p.rows / ((int64_t)cus * 16);
+    group = group < 1 ? 1 : (group > 64 / a->nD ? 64 / a->nD : group);
+    if (a->rows_per_wave > 0) group = a->rows_per_wave;     // tuning / testing override
+    p.group = (int32_t)group;
+    const int64_t waves = (p.rows + group - 1) / group;
+    hipLaunchKernelGGL(ivs::smile_delta_kernel, dim3((unsigned)((waves + ivs::SM_WAVES - 1) / ivs::SM_WAVES)),
+                       dim3(ivs::SM_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "smile_delta_kernel";
+    return check_launch("smile_delta_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

@@ -191,6 +191,73 @@ def snapshot_assemble(date_ns, iv, underlying, row_off, cells, strike, expiry_ns
     return out
 
 
+DEFAULT_DELTAS = (-0.10, -0.25, 0.5, 0.25, 0.10)      # rule D3: 10d put, 25d put, ATM, 25d call, 10d call
+
+
+def delta_targets(deltas):
+    """Rule D3 on the host: signed deltas -> z = inv_cdf(call delta), a put delta d in (-1, 0) meaning the call delta 1 + d.
+    Anything outside (-1, 0) and (0, 1), an empty list or more than 16 targets raises ValueError."""
+    from statistics import NormalDist
+    deltas = [float(d) for d in deltas]
+    if not 1 <= len(deltas) <= _lib.SM_MAX_TARGETS:
+        raise ValueError(f"{len(deltas)} target deltas: between 1 and {_lib.SM_MAX_TARGETS} are supported")
+    inv = NormalDist().inv_cdf
+    z = []
+    for d in deltas:
+        if 0.0 < d < 1.0:
+            z.append(inv(d))
+        elif -1.0 < d < 0.0:
+            z.append(inv(1.0 + d))
+        else:
+            raise ValueError(f"target delta {d!r} is outside (-1, 0) and (0, 1)")
+    return z
+
+
+def smile_delta_points(vol, Kq, Tq, spot, deltas=DEFAULT_DELTAS, rate: float = 0.0, *, out=None, stream=None,
+                       rows_per_wave: int = 0):
+    """Delta-quoted smile points of a batch of surfaces (ivs_smile_delta_points_f64; rules D1-D6 of DESIGN.md section 9).
+    vol float64 [B,mT,mK] (the `out` of surface_batch); Kq [mK] or [B,mK]; Tq [mT] or [B,mT]; spot [B]; all CUDA tensors.
+    deltas: 1..16 signed targets (call deltas in (0,1), put deltas in (-1,0), ATM = 0.5); rate: the scalar r of d1.
+    `out`: optional dict of preallocated outputs (keys vol, strike float64 [B,mT,nD], flags int32 [B,mT,nD]).
+    rows_per_wave: 0 lets the call choose how many rows share a wavefront; 1..64 // nD forces it (tuning / testing; the
+    results are the same bit for bit).
+    Returns dict(vol, strike, flags) of device tensors; flags are the _lib.SM_* bits."""
+    import ctypes
+    z = delta_targets(deltas)
+    torch = require_device()
+    lib = _lib.load()
+    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if vol.dim() != 3:
+        raise ValueError("vol must be [B, mT, mK]")
+    B, mT, mK = vol.shape
+    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
+        raise ValueError("Kq must be [mK] or [B, mK]")
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+    nD = len(z)
+    out = dict(out or {})
+    for k, dt in (("vol", torch.float64), ("strike", torch.float64), ("flags", torch.int32)):
+        t = out.get(k)
+        if t is None:
+            out[k] = torch.empty((B, mT, nD), dtype=dt, device=vol.device)
+        elif tuple(t.shape) != (B, mT, nD) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {(B, mT, nD)}")
+    zbuf = (ctypes.c_double * nD)(*z)
+    a = _lib.SmileArgs()
+    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
+    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.z = ctypes.cast(zbuf, ctypes.POINTER(ctypes.c_double))
+    a.mK, a.mT, a.nD, a.B = mK, mT, nD, B
+    a.q_vol, a.q_strike, a.q_flags = _ptr(out["vol"]), _ptr(out["strike"]), _ptr(out["flags"])
+    a.rows_per_wave = int(rows_per_wave)
+    rc = lib.ivs_smile_delta_points_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
+    _lib.check(rc, "ivs_smile_delta_points_f64")
+    return out
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -8,6 +8,8 @@ existing surface path (``engine.surface_batch``):
     b = SnapshotSurfaceBuilder(method="linear")
     res = b.build(long_frame)            # or a list of per-contract frames; one result per underlying
     df = b.to_frame(res)                 # underlying, date, spot, tenor, moneyness, iv, status
+    q = b.smiles(res)                    # delta-quoted points (ATM, 25d, 10d) per tenor: DESIGN.md section 9
+    pts, summ = smile_frame(q, res), smile_summary(q, res)
 
 The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
 NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
@@ -22,6 +24,7 @@ import numpy as np
 import pandas as pd
 
 from . import synth
+from .engine import DEFAULT_DELTAS, delta_targets      # rule D3: 10d put, 25d put, ATM, 25d call, 10d call
 
 YEAR_NS = 365 * 86400 * 10**9       # S2: E_c = date + time_to_maturity x YEAR, YEAR = 365 days (the synthetic data's convention)
 MINUTE_NS = 60 * 10**9
@@ -51,6 +54,19 @@ class SnapshotSurfaces:
     skipped_symbols: int             # contracts of the whole build() call skipped by rule S1
 
 
+@dataclass
+class SmileQuotes:
+    """One underlying's delta-quoted smile points (rules D1-D6).  vol, strike, flags are device tensors with the HIP backend
+    (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tenors: np.ndarray               # [mT]
+    deltas: np.ndarray               # [nD] signed targets, as asked
+    vol: object                      # [B, mT, nD]
+    strike: object                   # [B, mT, nD]
+    flags: object                    # [B, mT, nD] int32, IVS_SM_*
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -70,6 +86,12 @@ class HipBackend:
         torch = engine.require_device()
         return engine.surface_batch(torch.from_numpy(np.ascontiguousarray(K)).cuda(), T, sigma, Kq,
                                     torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), method, stream=self.stream)
+
+    def smile_points(self, vol, Kq, Tq, spot, deltas, rate):
+        from . import engine
+        torch = engine.require_device()
+        return engine.smile_delta_points(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, deltas, rate,
+                                         stream=self.stream)
 
 
 def _host(a):
@@ -196,6 +218,20 @@ class SnapshotSurfaceBuilder:
                                             a["spot"], a["quotes"], a["Kq"], out, status, skipped))
         return results
 
+    # ------------------------------------------------------------------ smiles
+    def smiles(self, results: Sequence[SnapshotSurfaces], deltas=None, rate: float = 0.0) -> List[SmileQuotes]:
+        """Delta-quoted points of every surface of `results` (rules D1-D6): one SmileQuotes per underlying, arrays on the
+        device.  deltas: signed targets (default DEFAULT_DELTAS); a value outside (-1, 0) and (0, 1) raises ValueError."""
+        deltas = DEFAULT_DELTAS if deltas is None else tuple(float(d) for d in deltas)
+        delta_targets(deltas)                                                # D3: reject bad targets before any launch
+        be = self._backend or HipBackend()
+        quotes = []
+        for r in results:
+            q = be.smile_points(r.out, r.Kq, r.tenors, r.spot, deltas, float(rate))
+            quotes.append(SmileQuotes(r.underlying, r.dates, r.tenors, np.asarray(deltas, np.float64), q["vol"], q["strike"],
+                                      q["flags"]))
+        return quotes
+
     # ------------------------------------------------------------------ output
     @staticmethod
     def to_frame(results: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
@@ -223,3 +259,64 @@ class SnapshotSurfaceBuilder:
                                  "status": pd.Series(dtype=np.int32)})
         df = pd.concat(parts, ignore_index=True)
         return df.sort_values(["underlying", "date", "tenor", "moneyness"], kind="stable").reset_index(drop=True)
+
+
+def _pct(d: float) -> str:
+    return f"{round(abs(d) * 100.0, 6):g}"
+
+
+def smile_frame(quotes: Sequence[SmileQuotes], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Long frame of the smile points of every snapshot with quotes > 0: columns underlying, date, spot, tenor, delta,
+    strike, iv, flags, ordered by (underlying, date, tenor) with the targets of a tenor in the order they were asked."""
+    parts = []
+    for q, r in zip(quotes, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        vol, strike, flags = _host(q.vol)[keep], _host(q.strike)[keep], _host(q.flags)[keep]
+        n, mT, nD = vol.shape
+        per = mT * nD
+        parts.append(pd.DataFrame({
+            "underlying": q.underlying,
+            "date": q.dates[keep].repeat(per),
+            "spot": np.repeat(_host(r.spot)[keep], per),
+            "tenor": np.tile(np.repeat(q.tenors, nD), n),
+            "delta": np.tile(np.tile(q.deltas, mT), n),
+            "strike": strike.reshape(-1),
+            "iv": vol.reshape(-1),
+            "flags": flags.reshape(-1).astype(np.int32)}))
+    if not parts:
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"),
+                             "spot": pd.Series(dtype=np.float64), "tenor": pd.Series(dtype=np.float64),
+                             "delta": pd.Series(dtype=np.float64), "strike": pd.Series(dtype=np.float64),
+                             "iv": pd.Series(dtype=np.float64), "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
+
+
+def smile_summary(quotes: Sequence[SmileQuotes], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Rule D7: per (underlying, date, tenor) of every snapshot with quotes > 0 the columns underlying, date, spot, tenor,
+    atm (the +0.5 target; NaN when it was not asked) and, for every |delta| other than 0.5 asked on both sides in ascending
+    order, rr_<pct> = iv(+delta) - iv(-delta) and bf_<pct> = 0.5 (iv(+delta) + iv(-delta)) - atm.  NaN where an
+    ingredient is.  All quotes must carry one and the same target list (ValueError otherwise)."""
+    parts, names = [], None
+    if any(not np.array_equal(q.deltas, quotes[0].deltas) for q in quotes):
+        raise ValueError("smile_summary: the quotes were built with different target lists")
+    for q, r in zip(quotes, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        vol = _host(q.vol)[keep]
+        n, mT, nD = vol.shape
+        d = [float(x) for x in q.deltas]
+        atm = vol[:, :, d.index(0.5)] if 0.5 in d else np.full((n, mT), np.nan)
+        cols = {"underlying": q.underlying, "date": q.dates[keep].repeat(mT), "spot": np.repeat(_host(r.spot)[keep], mT),
+                "tenor": np.tile(q.tenors, n), "atm": atm.reshape(-1)}
+        for x in sorted({abs(v) for v in d if abs(v) != 0.5 and -abs(v) in d and abs(v) in d}):
+            c, p = vol[:, :, d.index(x)], vol[:, :, d.index(-x)]
+            cols[f"rr_{_pct(x)}"] = (c - p).reshape(-1)
+            cols[f"bf_{_pct(x)}"] = (0.5 * (c + p) - atm).reshape(-1)
+        names = list(cols)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"),
+                             "spot": pd.Series(dtype=np.float64), "tenor": pd.Series(dtype=np.float64),
+                             "atm": pd.Series(dtype=np.float64)})
+    df = pd.concat(parts, ignore_index=True)[names]
+    return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
