@@ -28,6 +28,7 @@ MINUTE_TABLE = "minute_candles"
 CANDLE_TABLE = "reconstructed_candles"
 SURFACE_TABLE = "iv_surfaces"
 SMILE_TABLE = "iv_smiles"
+ARBITRAGE_TABLE = "iv_arbitrage"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -239,6 +240,32 @@ class CompleteOptimizedPipeline:
         print(f"\nSMILES COMPLETE: {duration:.1f}s, underlyings {len(results)}, rows {n_rows:,}")
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "duration": duration}
 
+    def run_arbitrage(self) -> dict:
+        """Static-arbitrage report: the snapshots of run_surfaces, then the calendar / butterfly
+        check of every node on the device, and one `iv_arbitrage` table per underlying (rule A8: columns underlying, date,
+        spot, evaluated, calendar, butterfly, local_vol_nodes, min_numerator, min_density_factor, arbitrage_free)."""
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, arbitrage_frame
+        print("\nARBITRAGE: STATIC-ARBITRAGE REPORT (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the arbitrage report"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_free = 0
+        for res, rep in zip(results, builder.arbitrage(results)):
+            table = arbitrage_frame([rep], [res])
+            self.store.write_table(ARBITRAGE_TABLE, res.underlying, table)
+            n_rows += len(table)
+            free = int(table["arbitrage_free"].sum())
+            n_free += free
+            print(f"  {res.underlying}: {len(table)} snapshots, {free} arbitrage-free")
+        duration = time.time() - start
+        print(f"\nARBITRAGE COMPLETE: {duration:.1f}s, underlyings {len(results)}, rows {n_rows:,}, arbitrage-free {n_free:,}")
+        return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "arbitrage_free_snapshots": n_free,
+                "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -272,7 +299,7 @@ class CompleteOptimizedPipeline:
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -311,6 +338,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_surfaces()
             elif args.task == "smiles":
                 result = pipeline.run_smiles()
+            elif args.task == "arbitrage":
+                result = pipeline.run_arbitrage()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -309,6 +309,42 @@ typedef struct ivs_smile_args {
 int ivs_smile_delta_points_f64(const ivs_smile_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Static-arbitrage report, risk-neutral density and Dupire local volatility off snapshot surfaces (DESIGN.md section 10,
+ * rules A1-A8; additive to ABI 5).  A 5-point stencil in (ln k, tau) over the total variance w = vol^2 tau of every node
+ * of `vol` (the `out` of ivs_surface_batch_f64), with the inputs of ivs_smile_delta_points_f64:
+ *
+ *   vol [B][mT][mK], Kq / kq_stride, Tq / tq_stride, spot [B], rate      as for the smile points; a stride is 0 (one
+ *                                      shared grid) or mK / mT (one grid per snapshot)
+ *   flags [B][mT][mK] (int32)          IVS_AR_*: DEAD = the node's vol or strike, the snapshot's spot or the row's tenor is
+ *                                      not a finite positive number; NO_STENCIL = a strike neighbour is missing or
+ *                                      invalid, a strike spacing is not > 0, or no tenor neighbour counts; otherwise
+ *                                      CALENDAR (Dupire numerator N < 0) | BUTTERFLY (density factor g < 0), 0 = clean
+ *   counts [B][4] (int32)              nodes evaluated (neither DEAD nor NO_STENCIL), CALENDAR nodes, BUTTERFLY nodes,
+ *                                      nodes with a finite local vol
+ *   worst [B][2]                       min N and min g over the evaluated nodes, NaN if there are none
+ *   local_vol, density [B][mT][mK]     optional (NULL = not written): sqrt(N / g) where N >= 0 and g > 0, and the
+ *                                      undiscounted d2C/dK2 (negative where g is); NaN at DEAD / NO_STENCIL nodes
+ * Every element of every requested output is written, bitwise deterministically (plain stores, no atomics), in ONE
+ * launch.  mK >= 3, mT >= 2 and B*mT < 2^31 are checked (IVS_ERANGE); B == 0 is a no-op.  No workspace.
+ */
+enum {
+    IVS_AR_CALENDAR   = 1,
+    IVS_AR_BUTTERFLY  = 2,
+    IVS_AR_NO_STENCIL = 4,
+    IVS_AR_DEAD       = 8
+};
+typedef struct ivs_arbitrage_args {
+    const double* vol;
+    const double* Kq; int64_t kq_stride;
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    int32_t mK, mT; int64_t B;
+    int32_t* flags; int32_t* counts; double* worst;
+    double* local_vol; double* density; /* either may be NULL */
+} ivs_arbitrage_args;
+int ivs_surface_arbitrage_f64(const ivs_arbitrage_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -355,8 +391,8 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
                                const uint32_t* words, int64_t n_words, double* out, uint8_t* valid, int64_t* rng_tail,
                                void* workspace, size_t workspace_bytes, void* stream);
 
-/* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 call on this
- * thread dispatched to (host string) */
+/* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
+ * ivs_surface_arbitrage_f64 call on this thread dispatched to (host string) */
 const char* ivs_last_kernel(void);
 
 /*

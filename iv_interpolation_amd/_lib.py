@@ -15,6 +15,7 @@ LINEAR, CUBIC, CUBICSPLINE, SLINEAR = 0, 1, 2, 3
 ST_OK, ST_TOO_FEW_KNOTS, ST_BAD_SHAPE, ST_ILL_CONDITIONED = 0, 1, 2, 4
 SM_OK, SM_NO_CROSSING, SM_AMBIGUOUS, SM_DEAD = 0, 1, 2, 4      # IVS_SM_*: per-target flags of the smile points
 SM_MAX_TARGETS = 16
+AR_CALENDAR, AR_BUTTERFLY, AR_NO_STENCIL, AR_DEAD = 1, 2, 4, 8    # IVS_AR_*: per-node flags of the arbitrage report
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -96,6 +97,13 @@ class SmileArgs(C.Structure):
                 ("q_vol", _p), ("q_strike", _p), ("q_flags", _p), ("rows_per_wave", _i32)]
 
 
+class ArbitrageArgs(C.Structure):
+    """ivs_arbitrage_args of include/ivs.h (field for field)."""
+    _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
+                ("spot", _p), ("rate", C.c_double), ("mK", _i32), ("mT", _i32), ("B", _i64),
+                ("flags", _p), ("counts", _p), ("worst", _p), ("local_vol", _p), ("density", _p)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -126,6 +134,7 @@ SIGNATURES = {
     "ivs_surface_workspace_bytes": (_sz, [_i64, _i32]),
     "ivs_snapshot_assemble_f64": (C.c_int, [C.POINTER(SnapshotArgs), _p, _sz, _p]),
     "ivs_smile_delta_points_f64": (C.c_int, [C.POINTER(SmileArgs), _p, _sz, _p]),
+    "ivs_surface_arbitrage_f64": (C.c_int, [C.POINTER(ArbitrageArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }
@@ -156,7 +165,9 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
-            raise EngineUnavailable(f"{LIB_PATH} does not export {name}") from e
+            raise EngineUnavailable(
+                f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild it with "
+                "`python -c 'import __graft_entry__ as g; g.build()'`") from e
         fn.restype = res
         fn.argtypes = args
     if lib.ivs_version() != ABI_VERSION:

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/ivs.h"
+#include "ivs_arbitrage.hpp"
 #include "ivs_bridge.hpp"
 #include "ivs_candles.hpp"
 #include "ivs_interp1d.hpp"
@@ -401,6 +402,49 @@ int ivs_smile_delta_points_f64(const ivs_smile_args* a, void* workspace, size_t 
                        dim3(ivs::SM_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
     g_last_kernel = "smile_delta_kernel";
     return check_launch("smile_delta_kernel");
+}
+
+int ivs_surface_arbitrage_f64(const ivs_arbitrage_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_surface_arbitrage_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->mK < 3) return fail(IVS_ERANGE, "%s: mK=%d < 3: the strike stencil needs three nodes", fn, a->mK);
+    if (a->mT < 2) return fail(IVS_ERANGE, "%s: mT=%d < 2: the tenor stencil needs two rows", fn, a->mT);
+    if (a->B == 0) return IVS_OK;
+    if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->flags || !a->counts || !a->worst)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
+        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    ivs::ArbParams p{};
+    p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
+    p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate;
+    p.mK = a->mK; p.mT = a->mT; p.B = a->B;
+    p.flags = a->flags; p.counts = a->counts; p.worst = a->worst; p.local_vol = a->local_vol; p.density = a->density;
+    // A snapshot is cut into 64-strike chunks x strips of tenor rows, one wavefront each.  Whole snapshots per wavefront
+    // while the batch fills the device (~16 wavefronts per CU); below that, strips of at least 4 rows (each strip reads its
+    // two neighbouring rows again).  A workgroup takes as many snapshots as give each of its wavefronts a task.
+    int dev, cus;
+    current_device(dev, cus);
+    p.nchunk = (a->mK + 63) / 64;
+    const int64_t whole = a->B * p.nchunk, want = (int64_t)cus * 16;
+    int64_t nstrip = (want + whole - 1) / whole;
+    const int64_t most = a->mT / 4 > 1 ? a->mT / 4 : 1;
+    nstrip = nstrip < 1 ? 1 : (nstrip > most ? most : nstrip);
+    p.strip = (int32_t)((a->mT + nstrip - 1) / nstrip);
+    p.nstrip = (a->mT + p.strip - 1) / p.strip;
+    const int per_snap = p.nchunk * p.nstrip;
+    int spw = (ivs::AR_WAVES + per_snap - 1) / per_snap;
+    p.spw = spw < 1 ? 1 : (spw > ivs::AR_MAX_SPW ? ivs::AR_MAX_SPW : spw);
+    const int64_t grid = (a->B + p.spw - 1) / p.spw;
+    hipLaunchKernelGGL(ivs::surface_arbitrage_kernel, dim3((unsigned)grid), dim3(ivs::AR_WAVES * 64), 0,
+                       static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "surface_arbitrage_kernel";
+    return check_launch("surface_arbitrage_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

@@ -258,6 +258,52 @@ def smile_delta_points(vol, Kq, Tq, spot, deltas=DEFAULT_DELTAS, rate: float = 0
     return out
 
 
+def surface_arbitrage(vol, Kq, Tq, spot, rate: float = 0.0, *, local_vol: bool = True, density: bool = True, out=None,
+                      stream=None):
+    """Static-arbitrage report, Dupire local vol and risk-neutral density of a batch of surfaces
+    (ivs_surface_arbitrage_f64; rules A1-A7 of DESIGN.md section 10).  vol float64 [B,mT,mK] (the `out` of surface_batch);
+    Kq [mK] or [B,mK]; Tq [mT] or [B,mT]; spot [B]; all CUDA tensors; mK >= 3, mT >= 2.  rate: the scalar r.
+    local_vol / density: False leaves that field out (it is neither computed nor written).
+    `out`: optional dict of preallocated outputs (keys flags int32 [B,mT,mK], counts int32 [B,4], worst float64 [B,2],
+    local_vol, density float64 [B,mT,mK]).
+    Returns dict(flags, counts, worst, local_vol, density) of device tensors (None for a field left out); flags are the
+    _lib.AR_* bits, counts = evaluated, calendar, butterfly, finite local-vol nodes, worst = min numerator, min g."""
+    torch = require_device()
+    lib = _lib.load()
+    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if vol.dim() != 3:
+        raise ValueError("vol must be [B, mT, mK]")
+    B, mT, mK = vol.shape
+    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
+        raise ValueError("Kq must be [mK] or [B, mK]")
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+    out = dict(out or {})
+    want = {"flags": ((B, mT, mK), torch.int32, True), "counts": ((B, 4), torch.int32, True),
+            "worst": ((B, 2), torch.float64, True), "local_vol": ((B, mT, mK), torch.float64, bool(local_vol)),
+            "density": ((B, mT, mK), torch.float64, bool(density))}
+    for k, (shape, dt, on) in want.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    a = _lib.ArbitrageArgs()
+    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
+    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.mK, a.mT, a.B = mK, mT, B
+    a.flags, a.counts, a.worst = _ptr(out["flags"]), _ptr(out["counts"]), _ptr(out["worst"])
+    a.local_vol, a.density = _ptr(out["local_vol"]), _ptr(out["density"])
+    rc = lib.ivs_surface_arbitrage_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
+    _lib.check(rc, "ivs_surface_arbitrage_f64")
+    return {k: out[k] for k in want}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -10,6 +10,8 @@ existing surface path (``engine.surface_batch``):
     df = b.to_frame(res)                 # underlying, date, spot, tenor, moneyness, iv, status
     q = b.smiles(res)                    # delta-quoted points (ATM, 25d, 10d) per tenor: DESIGN.md section 9
     pts, summ = smile_frame(q, res), smile_summary(q, res)
+    a = b.arbitrage(res)                 # static-arbitrage flags, local vol, density: DESIGN.md section 10
+    rep, lv = arbitrage_frame(a, res), local_vol_frame(a, res)
 
 The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
 NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
@@ -67,6 +69,22 @@ class SmileQuotes:
     flags: object                    # [B, mT, nD] int32, IVS_SM_*
 
 
+@dataclass
+class ArbitrageReport:
+    """One underlying's static-arbitrage report (rules A1-A7).  The arrays are device tensors with the HIP backend (host
+    arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tenors: np.ndarray               # [mT]
+    moneyness: np.ndarray            # [mK]
+    rate: float
+    flags: object                    # [B, mT, mK] int32, IVS_AR_*
+    counts: object                   # [B, 4] int32: evaluated, calendar, butterfly, finite local-vol nodes
+    worst: object                    # [B, 2]: min Dupire numerator, min density factor g
+    local_vol: object                # [B, mT, mK]
+    density: object                  # [B, mT, mK]
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -92,6 +110,12 @@ class HipBackend:
         torch = engine.require_device()
         return engine.smile_delta_points(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, deltas, rate,
                                          stream=self.stream)
+
+    def arbitrage(self, vol, Kq, Tq, spot, rate):
+        from . import engine
+        torch = engine.require_device()
+        return engine.surface_arbitrage(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate,
+                                        stream=self.stream)
 
 
 def _host(a):
@@ -232,6 +256,18 @@ class SnapshotSurfaceBuilder:
                                       q["flags"]))
         return quotes
 
+    # ------------------------------------------------------------------ arbitrage
+    def arbitrage(self, results: Sequence[SnapshotSurfaces], rate: float = 0.0) -> List[ArbitrageReport]:
+        """Static-arbitrage flags, Dupire local vol and density of every surface of `results` (rules A1-A7): one
+        ArbitrageReport per underlying, arrays on the device."""
+        be = self._backend or HipBackend()
+        reports = []
+        for r in results:
+            a = be.arbitrage(r.out, r.Kq, r.tenors, r.spot, float(rate))
+            reports.append(ArbitrageReport(r.underlying, r.dates, r.tenors, r.moneyness, float(rate), a["flags"], a["counts"],
+                                           a["worst"], a["local_vol"], a["density"]))
+        return reports
+
     # ------------------------------------------------------------------ output
     @staticmethod
     def to_frame(results: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
@@ -320,3 +356,55 @@ def smile_summary(quotes: Sequence[SmileQuotes], snapshots: Sequence[SnapshotSur
                              "atm": pd.Series(dtype=np.float64)})
     df = pd.concat(parts, ignore_index=True)[names]
     return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
+
+
+def arbitrage_frame(reports: Sequence[ArbitrageReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Rule A8: one row per snapshot with quotes > 0, ordered by (underlying, date): columns underlying, date, spot,
+    evaluated, calendar, butterfly, local_vol_nodes, min_numerator, min_density_factor, arbitrage_free (evaluated > 0 and
+    no calendar and no butterfly node)."""
+    parts = []
+    for a, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        c, w = _host(a.counts)[keep].astype(np.int32), _host(a.worst)[keep]
+        parts.append(pd.DataFrame({
+            "underlying": a.underlying,
+            "date": a.dates[keep],
+            "spot": _host(r.spot)[keep],
+            "evaluated": c[:, 0], "calendar": c[:, 1], "butterfly": c[:, 2], "local_vol_nodes": c[:, 3],
+            "min_numerator": w[:, 0], "min_density_factor": w[:, 1],
+            "arbitrage_free": (c[:, 0] > 0) & (c[:, 1] == 0) & (c[:, 2] == 0)}))
+    if not parts:
+        i32, f64 = pd.Series(dtype=np.int32), pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "evaluated": i32, "calendar": i32, "butterfly": i32, "local_vol_nodes": i32,
+                             "min_numerator": f64, "min_density_factor": f64, "arbitrage_free": pd.Series(dtype=bool)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def local_vol_frame(reports: Sequence[ArbitrageReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Long frame of the nodes of every snapshot with quotes > 0, in to_frame's order: columns underlying, date, spot, tenor,
+    moneyness, iv, local_vol, density, flags."""
+    parts = []
+    for a, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        iv = _host(r.out)[keep]
+        n, mT, mK = iv.shape
+        per = mT * mK
+        parts.append(pd.DataFrame({
+            "underlying": a.underlying,
+            "date": a.dates[keep].repeat(per),
+            "spot": np.repeat(_host(r.spot)[keep], per),
+            "tenor": np.tile(np.repeat(a.tenors, mK), n),
+            "moneyness": np.tile(np.tile(a.moneyness, mT), n),
+            "iv": iv.reshape(-1),
+            "local_vol": _host(a.local_vol)[keep].reshape(-1),
+            "density": _host(a.density)[keep].reshape(-1),
+            "flags": _host(a.flags)[keep].reshape(-1).astype(np.int32)}))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "tenor": f64, "moneyness": f64, "iv": f64, "local_vol": f64, "density": f64,
+                             "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "tenor", "moneyness"], kind="stable").reset_index(drop=True)
