@@ -24,6 +24,7 @@ namespace {
 
 thread_local char g_err[512] = "";
 thread_local const char* g_last_kernel = "";
+thread_local char g_kernel_name[64] = "";             // ivs_last_kernel() of the surface fast paths: family<method>
 // diagnostics (ivs_debug_stamps): per calling thread, like the error string
 thread_local unsigned long long* g_stamp_buf = nullptr;   // device buffer for the diagnostic (stamped) dense kernel
 thread_local int64_t g_stamp_cap = 0;
@@ -41,6 +42,13 @@ int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(IVS_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
     return IVS_OK;
+}
+
+// family<method>; a family that already carries its argument ("surface_dense_kernel<stamp>") is reported as it is
+void set_last_kernel(const char* family, int method) {
+    if (strchr(family, '<')) snprintf(g_kernel_name, sizeof(g_kernel_name), "%s", family);
+    else snprintf(g_kernel_name, sizeof(g_kernel_name), "%s<%s>", family, ivs::method_name(method));
+    g_last_kernel = g_kernel_name;
 }
 
 bool valid_method(int m) { return m >= IVS_LINEAR && m <= IVS_BFILL; }
@@ -197,10 +205,7 @@ int gather_impl(const char* fn, const void* src, int64_t src_stride, const int32
     if (idx_stride < n || out_stride < n) return fail(IVS_EINVAL, "%s: stride smaller than row count", fn);
     if (src_stride > 0x7fffffffLL) return fail(IVS_ERANGE, "%s: %lld source rows exceed the int32 gather index", fn, (long long)src_stride);
     ivs::GatherParams p{src, src_stride, idx, idx_stride, idx_row, n_cols, n, out, out_stride};
-    int64_t blocks = (n + 255) / 256;
-    const int64_t cap = (int64_t)num_cu() * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(ivs::gather_rows_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, missing);
+    hipLaunchKernelGGL(ivs::gather_rows_kernel<T>, dim3((unsigned)ivs::capped_blocks(n, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p, missing);
     return check_launch(fn);
 }
 }  // namespace
@@ -228,10 +233,7 @@ int ivs_frame_rows(const int64_t* q_off, int64_t n_series, int64_t total_queries
         return fail(IVS_EINVAL, "ivs_frame_rows: null pointer");
     if (chan_stride < total_queries) return fail(IVS_EINVAL, "ivs_frame_rows: chan_stride < total_queries");
     ivs::FrameRowsParams p{q_off, n_series, total_queries, first_ns, chan, chan_stride, n_channels, sym_code, status, needs, date_ns, keep};
-    int64_t blocks = (total_queries + 255) / 256;
-    const int64_t cap = (int64_t)num_cu() * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(ivs::frame_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    hipLaunchKernelGGL(ivs::frame_rows_kernel, dim3((unsigned)ivs::capped_blocks(total_queries, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return check_launch("frame_rows_kernel");
 }
 
@@ -296,12 +298,8 @@ int ivs_frame_columns_f64(const ivs_frame_args* a, void* workspace, size_t works
     p.xq = nullptr; p.q_off = a->q_off; p.total_q = a->total_queries;
     p.out = a->chan_out; p.out_stride = a->chan_stride; p.status = a->status; p.method = a->method;
     p.greeks = nullptr;
-    if (a->total_src > 0) {
-        int64_t cb = (a->total_src + 255) / 256;
-        const int64_t cap = (int64_t)num_cu() * 16;
-        if (cb > cap) cb = cap;
-        hipLaunchKernelGGL(i64_to_f64_kernel, dim3((unsigned)cb), dim3(256), 0, st, a->src_pos, xk, a->total_src);
-    }
+    if (a->total_src > 0)
+        hipLaunchKernelGGL(i64_to_f64_kernel, dim3((unsigned)ivs::capped_blocks(a->total_src, num_cu())), dim3(256), 0, st, a->src_pos, xk, a->total_src);
     if (a->n_channels > 0) {
         hipLaunchKernelGGL(ivs::interp1d_prepare_kernel, dim3((unsigned)(a->n_series * a->n_channels)), dim3(256), 0, st, p);
         const int rc = check_launch("interp1d_prepare_kernel");
@@ -317,11 +315,9 @@ int ivs_frame_columns_f64(const ivs_frame_args* a, void* workspace, size_t works
     f.g_strike = a->g_strike; f.g_rate = a->g_rate; f.g_put = a->g_put; f.strike_src = a->strike_src; f.rate_src = a->rate_src; f.put_src = a->put_src;
     f.ch_iv = a->ch_iv; f.ch_S = a->ch_underlying; f.ch_T = a->ch_ttm; f.greeks = a->greeks; f.greeks_stride = a->greeks_stride;
     const dim3 fgrid((unsigned)((a->total_queries + ivs::FR_ROWS - 1) / ivs::FR_ROWS));
-    switch (ivs::frame_method_class(p.method)) {
-        case 0: hipLaunchKernelGGL(ivs::frame_fused_kernel<0>, fgrid, dim3(256), 0, st, f, p); break;
-        case 1: hipLaunchKernelGGL(ivs::frame_fused_kernel<1>, fgrid, dim3(256), 0, st, f, p); break;
-        default: hipLaunchKernelGGL(ivs::frame_fused_kernel<2>, fgrid, dim3(256), 0, st, f, p); break;
-    }
+    ivs::with_method(ivs::frame_method_class(p.method), ivs::Methods<0, 1, 2>{}, [&](auto c) {
+        hipLaunchKernelGGL(ivs::frame_fused_kernel<decltype(c)::value>, fgrid, dim3(256), 0, st, f, p);
+    });
     return check_launch("frame_fused_kernel");
 }
 
@@ -513,9 +509,7 @@ int ivs_bridge_candles_f64(const double* price, const double* volume, const int6
         int64_t nd = n_words / 2;                                   // doubles of the stream this call may look at
         const int64_t cap = (int64_t)ivs::bridge_acc_capacity(total_rows);
         if (nd > cap) { nd = cap; p.n_words = 2 * nd; }
-        int64_t ab = (nd + 255) / 256;
-        const int64_t abcap = (int64_t)num_cu() * 16;
-        if (ab > abcap) ab = abcap;
+        int64_t ab = ivs::capped_blocks(nd, num_cu());
         if (ab < 1) ab = 1;
         hipLaunchKernelGGL(ivs::bridge_accept_kernel, dim3((unsigned)ab), dim3(256), 0, st, p, nd);
         hipLaunchKernelGGL(ivs::bridge_gauss_walk_kernel, dim3(1), dim3(64), 0, st, p, nd);
@@ -525,13 +519,9 @@ int ivs_bridge_candles_f64(const double* price, const double* volume, const int6
     }
     int64_t grid = (int64_t)num_cu() * 8;
     if (grid > S) grid = S;
-    switch (strategy) {
-        case ivs::BR_SPREAD: hipLaunchKernelGGL(ivs::bridge_candles_kernel<ivs::BR_SPREAD>, dim3((unsigned)grid), dim3(64), 0, st, p); break;
-        case ivs::BR_MIDPOINT: hipLaunchKernelGGL(ivs::bridge_candles_kernel<ivs::BR_MIDPOINT>, dim3((unsigned)grid), dim3(64), 0, st, p); break;
-        case ivs::BR_TREND: hipLaunchKernelGGL(ivs::bridge_candles_kernel<ivs::BR_TREND>, dim3((unsigned)grid), dim3(64), 0, st, p); break;
-        case ivs::BR_PIPELINE: hipLaunchKernelGGL(ivs::bridge_candles_kernel<ivs::BR_PIPELINE>, dim3((unsigned)grid), dim3(64), 0, st, p); break;
-        default: hipLaunchKernelGGL(ivs::bridge_candles_kernel<ivs::BR_SIMPLE>, dim3((unsigned)grid), dim3(64), 0, st, p); break;
-    }
+    ivs::with_method(strategy, ivs::Methods<ivs::BR_SPREAD, ivs::BR_MIDPOINT, ivs::BR_TREND, ivs::BR_SIMPLE, ivs::BR_PIPELINE>{}, [&](auto strat) {
+        hipLaunchKernelGGL(ivs::bridge_candles_kernel<decltype(strat)::value>, dim3((unsigned)grid), dim3(64), 0, st, p);
+    });
     return check_launch("bridge_candles_kernel");
 }
 
@@ -544,10 +534,7 @@ int ivs_bs_greeks_f64(const double* S, const double* K, const double* T, const d
     if (!S || !K || !T || !r || !sigma || !delta || !gamma || !theta || !vega || !rho)
         return fail(IVS_EINVAL, "ivs_bs_greeks_f64: null pointer");
     ivs::GreeksParams p{S, K, T, r, sigma, is_put, default_is_put, n, delta, gamma, theta, vega, rho};
-    int64_t blocks = (n + 255) / 256;
-    int64_t cap = (int64_t)num_cu() * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(ivs::greeks_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    hipLaunchKernelGGL(ivs::greeks_kernel, dim3((unsigned)ivs::capped_blocks(n, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return check_launch("greeks_kernel");
 }
 
@@ -597,28 +584,26 @@ int ivs_surface_batch_f64(const double* K, const int64_t* k_off, int64_t k_strid
     cx.map_groups = (flags >> 8) & 0xff;
 
     if (!(flags & IVS_FLAG_FORCE_GENERIC)) {
-        const char* name = nullptr;
-        int64_t need_blocks = (int64_t)cx.num_cu * 8;
-        unsigned long long* dbg = (g_stamp_buf && g_stamp_cap >= need_blocks * ivs::D_NSTAMP) ? g_stamp_buf : nullptr;
-        int rc = (dbg || (flags & IVS_FLAG_ONE_PASS)) ? 0 : ivs::launch_surface_pass(p, cx, &name);
-        if (rc == 1) {
-            g_last_kernel = name;
-            return check_launch(name);
-        }
-        if (rc < 0) return fail(IVS_ELAUNCH, "ivs_surface_batch_f64: row-pass dispatch failed");
-        rc = ivs::launch_surface_dense(p, cx, &name, dbg, &g_last_grid);
-        if (rc == 1) {   // dispatched
-            g_last_kernel = name;
-            return check_launch(name);
-        }
-        if (rc < 0) return fail(IVS_ELAUNCH, "ivs_surface_batch_f64: dense dispatch failed");
-        if (!g_stamp_buf) {
-            rc = ivs::launch_surface_dense_var(p, cx, &name);
+        const int64_t need_blocks = (int64_t)cx.num_cu * 8;
+        cx.stamps = (g_stamp_buf && g_stamp_cap >= need_blocks * ivs::D_NSTAMP) ? g_stamp_buf : nullptr;
+        cx.grid_out = &g_last_grid;
+        // the fast paths in order; each answers 1 = dispatched, 0 = not covered (try the next), < 0 = launch error
+        const struct {
+            bool on;
+            int (*launch)(const ivs::SurfaceParams&, const ivs::LaunchCtx&, const char**);
+            const char* what;
+        } attempts[] = {{!cx.stamps && !(flags & IVS_FLAG_ONE_PASS), ivs::launch_surface_pass, "row-pass"},
+                        {true, ivs::launch_surface_dense, "dense"},
+                        {!g_stamp_buf, ivs::launch_surface_dense_var, "dense-var"}};
+        for (const auto& a : attempts) {
+            if (!a.on) continue;
+            const char* family = nullptr;
+            const int rc = a.launch(p, cx, &family);
             if (rc == 1) {
-                g_last_kernel = name;
-                return check_launch(name);
+                set_last_kernel(family, method);
+                return check_launch(g_last_kernel);
             }
-            if (rc < 0) return fail(IVS_ELAUNCH, "ivs_surface_batch_f64: dense-var dispatch failed");
+            if (rc < 0) return fail(IVS_ELAUNCH, "ivs_surface_batch_f64: %s dispatch failed", a.what);
         }
     }
 

@@ -20,6 +20,7 @@
 #include <cstddef>
 #include <cstdlib>
 
+#include "ivs_dispatch.hpp"
 #include "ivs_surface_generic.hpp"
 
 namespace ivs {
@@ -997,16 +998,13 @@ __global__ __launch_bounds__(64) void tq_tables_kernel(SurfaceParams p, TqShared
     }
     if (lane < 24) o->queue[lane * QUEUE_STRIDE] = 0ull;
 }
+using TableMethods = Methods<IVS_LINEAR, IVS_CUBIC, IVS_CUBICSPLINE, IVS_SLINEAR, IVS_PCHIP, IVS_AKIMA, IVS_NEAREST, IVS_ZERO,
+                             IVS_FROM_DERIVATIVES, IVS_QUADRATIC>;
 template <bool NTR>
 inline void launch_tq_tables(const SurfaceParams& p, TqShared* o, hipStream_t st) {
-#define IVS_TQ_CASE(M) case M: hipLaunchKernelGGL((tq_tables_kernel<M, NTR>), dim3(1), dim3(64), 0, st, p, o); break;
-    switch (p.method) {
-        IVS_TQ_CASE(IVS_LINEAR) IVS_TQ_CASE(IVS_CUBIC) IVS_TQ_CASE(IVS_CUBICSPLINE) IVS_TQ_CASE(IVS_SLINEAR)
-        IVS_TQ_CASE(IVS_PCHIP) IVS_TQ_CASE(IVS_AKIMA) IVS_TQ_CASE(IVS_NEAREST) IVS_TQ_CASE(IVS_ZERO) IVS_TQ_CASE(IVS_FROM_DERIVATIVES)
-        IVS_TQ_CASE(IVS_QUADRATIC)
-        default: break;
-    }
-#undef IVS_TQ_CASE
+    with_method(p.method, TableMethods{}, [&](auto m) {
+        hipLaunchKernelGGL((tq_tables_kernel<decltype(m)::value, NTR>), dim3(1), dim3(64), 0, st, p, o);
+    });
 }
 // fills the uniform part of TqTables from the published tables (scalar loads)
 __device__ __forceinline__ void tq_from_shared(const void* tqs, TqTables& tt, const double*& TT, const double*& W) {
@@ -1233,6 +1231,8 @@ struct LaunchCtx {
     unsigned char* ws = nullptr;
     size_t ws_bytes = 0;
     int map_groups = 0;
+    unsigned long long* stamps = nullptr;            // diagnostics (ivs_debug_stamps): buffer of the stamped dense kernel
+    int64_t* grid_out = nullptr;                     // diagnostics (ivs_debug_last_grid): receives the dense kernel's grid
 };
 constexpr int IVS_MAX_DEV = 64;
 constexpr size_t WS_TQ_BYTES = 8192;                 // TqShared at offset 0
@@ -1262,9 +1262,7 @@ inline bool launch_surface_generic(const SurfaceParams& p, const LaunchCtx& cx) 
     const size_t lds = generic_lds_bytes(p.nK, p.nT, method_is_cubic(p.method));
     if (lds > 160 * 1024) return false;
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(surface_generic_kernel<FILTER>), FILTER ? 1 : 0, cx.dev);
-    int per_cu = (int)((160 * 1024) / lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 16 ? 16 : per_cu);
-    int64_t grid = (int64_t)cx.num_cu * per_cu * 2;
+    int64_t grid = (int64_t)cx.num_cu * workgroups_per_cu(lds, 16) * 2;
     const int64_t work = FILTER ? (p.B + 63) / 64 : p.B;
     if (grid > work) grid = work;
     hipLaunchKernelGGL(surface_generic_kernel<FILTER>, dim3((unsigned)grid), dim3(64), lds, cx.st, p);
@@ -1302,64 +1300,60 @@ inline bool launch_tq_or_zero_queue(SurfaceParams& p, const LaunchCtx& cx, bool 
     return true;
 }
 
-#ifndef IVS_DIAG_MINIMAL      // diagnostic builds (tools/pass_api.hip) skip the launchers that instantiate every kernel
+// The tail of every fast-path launcher: surfaces the fast kernel tagged (missing quotes) go to the masked pass when the
+// batch is the fixed 64 x 16 form (shared T / Tq only, see launch_surface_masked), then the filtered generic kernel takes
+// whatever is still tagged (it returns at once when its counter is 0).
 inline bool launch_surface_masked(const SurfaceParams& p, const LaunchCtx& cx);      // ivs_surface_masked.hpp
-// Dense dispatch.  Returns 1 if dispatched (dense kernel + filtered generic redo pass), 0 if the
-// shape is not covered by a dense kernel.
-inline int launch_surface_dense(const SurfaceParams& p_in, const LaunchCtx& cx, const char** name,
-                                unsigned long long* dbg = nullptr, int64_t* grid_out = nullptr) {
+inline void launch_redo_tail(SurfaceParams& p, const LaunchCtx& cx, bool fixed64) {
+#ifndef IVS_DIAG_MINIMAL      // diagnostic builds (tools/pass_api.hip) skip the launchers that instantiate every kernel
+    if (fixed64 && launch_surface_masked(p, cx) && p.redo) ++p.redo;
+#endif
+    launch_surface_generic<true>(p, cx);
+}
+
+#ifndef IVS_DIAG_MINIMAL
+using DenseMethods = Methods<IVS_LINEAR, IVS_CUBIC, IVS_CUBICSPLINE, IVS_SLINEAR, IVS_PCHIP, IVS_AKIMA>;      // the one-pass kernels
+// Dense dispatch.  Returns 1 if dispatched (dense kernel + redo tail), 0 if the shape is not covered by a dense kernel,
+// -1 on a launch error.  *family: the kernel's name without its method.
+inline int launch_surface_dense(const SurfaceParams& p_in, const LaunchCtx& cx, const char** family) {
     SurfaceParams p = p_in;
-    hipStream_t st = cx.st;
     if (p.k_off || p.nK != DK || p.nT != DT) return 0;
     if (p.k_stride != 0 && p.k_stride < DK) return 0;
     if (reinterpret_cast<uintptr_t>(p.sigma) & 15) return 0;
     if (p.mT > D_MAX_MT) return 0;
     const size_t lds = dense_lds_bytes(p.mT);
     if (generic_lds_bytes(p.nK, p.nT) > 160 * 1024) return 0;
-    int per_cu = (int)((160 * 1024) / lds);
-    per_cu = per_cu > 8 ? 8 : per_cu;
-    int64_t grid = (int64_t)cx.num_cu * per_cu;
+    int64_t grid = (int64_t)cx.num_cu * workgroups_per_cu(lds, 8);
     if (grid > p.B) grid = p.B;
-    if (grid_out) *grid_out = grid;
+    if (cx.grid_out) *cx.grid_out = grid;
     p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);
     const bool tsh = p.t_stride == 0 && p.tq_stride == 0;
     const bool wl = p.mT <= D_WLDS_MAX_MT;
     if (!launch_tq_or_zero_queue<false>(p, cx, tsh, true)) return -1;
     if (p.map_groups > 16) p.map_groups = 16;
-    if (dbg) {   // diagnostic build: cubic and linear, shared T only
+    if (cx.stamps) {   // diagnostic run: cubic and linear, shared T only
         if (!tsh) return 0;
-        if (p.method == IVS_CUBIC) {
-            if (wl) hipLaunchKernelGGL((surface_dense_kernel<IVS_CUBIC, true, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, dbg);
-            else hipLaunchKernelGGL((surface_dense_kernel<IVS_CUBIC, true, false, true>), dim3((unsigned)grid), dim3(64), lds, st, p, dbg);
-        } else {
-            if (wl) hipLaunchKernelGGL((surface_dense_kernel<IVS_LINEAR, true, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, dbg);
-            else hipLaunchKernelGGL((surface_dense_kernel<IVS_LINEAR, true, false, true>), dim3((unsigned)grid), dim3(64), lds, st, p, dbg);
-        }
-        *name = "surface_dense_kernel<stamp>";
+        with_bool(p.method == IVS_CUBIC, [&](auto cubic) {
+            with_bool(wl, [&](auto w) {
+                hipLaunchKernelGGL((surface_dense_kernel<decltype(cubic)::value ? IVS_CUBIC : IVS_LINEAR, true, decltype(w)::value, true>), dim3((unsigned)grid), dim3(64),
+                                   lds, cx.st, p, cx.stamps);
+            });
+        });
+        *family = "surface_dense_kernel<stamp>";
         return hipGetLastError() == hipSuccess ? 1 : -1;
     }
-#define IVS_DENSE_CASE(M, NAME)                                                                            \
-    case M: {                                                                                              \
-        if (tsh && wl) hipLaunchKernelGGL((surface_dense_kernel<M, true, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, nullptr);        \
-        else if (tsh) hipLaunchKernelGGL((surface_dense_kernel<M, true, false, false>), dim3((unsigned)grid), dim3(64), lds, st, p, nullptr);        \
-        else if (wl) hipLaunchKernelGGL((surface_dense_kernel<M, false, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, nullptr);         \
-        else hipLaunchKernelGGL((surface_dense_kernel<M, false, false, false>), dim3((unsigned)grid), dim3(64), lds, st, p, nullptr);                \
-        *name = NAME;                                                                                      \
-        break;                                                                                             \
-    }
-    switch (p.method) {
-        IVS_DENSE_CASE(IVS_LINEAR, "surface_dense_kernel<linear>")
-        IVS_DENSE_CASE(IVS_CUBIC, "surface_dense_kernel<cubic>")
-        IVS_DENSE_CASE(IVS_CUBICSPLINE, "surface_dense_kernel<cubicspline>")
-        IVS_DENSE_CASE(IVS_SLINEAR, "surface_dense_kernel<slinear>")
-        IVS_DENSE_CASE(IVS_PCHIP, "surface_dense_kernel<pchip>")
-        IVS_DENSE_CASE(IVS_AKIMA, "surface_dense_kernel<akima>")
-        default: return 0;
-    }
-#undef IVS_DENSE_CASE
+    const bool known = with_method(p.method, DenseMethods{}, [&](auto m) {
+        with_bool(tsh, [&](auto t) {
+            with_bool(wl, [&](auto w) {
+                hipLaunchKernelGGL((surface_dense_kernel<decltype(m)::value, decltype(t)::value, decltype(w)::value, false>), dim3((unsigned)grid), dim3(64), lds, cx.st, p,
+                                   nullptr);
+            });
+        });
+    });
+    if (!known) return 0;
+    *family = "surface_dense_kernel";
     if (hipGetLastError() != hipSuccess) return -1;
-    if (launch_surface_masked(p, cx) && p.redo) ++p.redo;      // tagged surfaces (missing quotes): compaction kernel first (shared T / Tq only) ...
-    launch_surface_generic<true>(p, cx);     // ... then whatever is still tagged (returns at once when its counter is 0)
+    launch_redo_tail(p, cx, true);
     return 1;
 }
 

@@ -600,10 +600,7 @@ inline bool var_work_lists(const SurfaceParams& p, const LaunchCtx& cx, VarWork&
         counts = reinterpret_cast<int32_t*>(cx.ws + WS_TQ_BYTES);
         lists = reinterpret_cast<VarItem*>(cx.ws + WS_TQ_BYTES + WS_COUNTS_BYTES);
         if (hipMemsetAsync(counts, 0, WS_COUNTS_BYTES, cx.st) != hipSuccess) return false;
-        int64_t cb = (p.B + 1023) / 1024;
-        const int64_t cap = (int64_t)cx.num_cu * 8;
-        if (cb > cap) cb = cap;
-        hipLaunchKernelGGL(var_classify_kernel, dim3((unsigned)cb), dim3(256), 0, cx.st, p, lists, lists + p.B, counts);
+        hipLaunchKernelGGL(var_classify_kernel, dim3((unsigned)capped_blocks(p.B, cx.num_cu, 1024, 8)), dim3(256), 0, cx.st, p, lists, lists + p.B, counts);
     }
     w.wl1 = VarList{lists, counts, 0};
     w.wl2 = VarList{lists ? lists + p.B : nullptr, counts ? counts + 1 : nullptr, 1};

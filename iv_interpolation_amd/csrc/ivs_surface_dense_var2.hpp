@@ -458,11 +458,10 @@ __global__ __launch_bounds__(128, 2) void surface_dense_var2_kernel(SurfaceParam
 
 #ifndef IVS_DIAG_MINIMAL
 // Dispatch for variable strike counts: class 4..64 on the one-wavefront kernel, class 65..128 on the two-wavefront
-// kernel, then the filtered generic redo pass.  Returns 1 if dispatched, 0 if the batch is not covered.
-// Scratch (ragged work lists + counters, batch-wide maturity tables) comes from the caller's workspace: no allocation.
-inline int launch_surface_dense_var(const SurfaceParams& p_in, const LaunchCtx& cx, const char** name) {
+// kernel, then the filtered generic redo pass.  Returns 1 if dispatched, 0 if the batch is not covered, -1 on a launch
+// error.  Scratch (ragged work lists + counters, batch-wide maturity tables) comes from the caller's workspace: no allocation.
+inline int launch_surface_dense_var(const SurfaceParams& p_in, const LaunchCtx& cx, const char** family) {
     SurfaceParams p = p_in;
-    hipStream_t st = cx.st;
     if (p.nT < 4 || p.nT > DT || p.mT > D_MAX_MT) return 0;
     const bool tsh = p.t_stride == 0 && p.tq_stride == 0;
     if (p.nK < 4 || p.nK > 128) return 0;
@@ -475,52 +474,25 @@ inline int launch_surface_dense_var(const SurfaceParams& p_in, const LaunchCtx& 
     VarWork vw;
     if (!var_work_lists(p, cx, vw)) return -1;
     auto grid_for = [&](size_t lds) {
-        int per_cu = (int)((160 * 1024) / lds);
-        per_cu = per_cu > 8 ? 8 : (per_cu < 1 ? 1 : per_cu);
-        int64_t g = (int64_t)cx.num_cu * per_cu;
-        return g > p.B ? p.B : g;
+        const int64_t g = (int64_t)cx.num_cu * workgroups_per_cu(lds, 8);
+        return dim3((unsigned)(g > p.B ? p.B : g));
     };
-#define IVS_VAR_LAUNCH1(M)                                                                                           \
-    {                                                                                                                \
-        const size_t lds = dense_var_lds_bytes<1>(p.mT);                                                             \
-        const int64_t grid = grid_for(lds);                                                                          \
-        if (wl && tsh) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);    \
-        else if (tsh) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, false, true>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);    \
-        else if (wl) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);     \
-        else hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, false, false>), dim3((unsigned)grid), dim3(64), lds, st, p, vw.wl1);            \
-    }
-#define IVS_VAR_LAUNCH2(M)                                                                                           \
-    {                                                                                                                \
-        const size_t lds = dense_var2_lds_bytes(p.mT);          /* 40 KB: below the 64 KiB default limit */          \
-        const int64_t grid = grid_for(lds);                                                                          \
-        if (wl && tsh) hipLaunchKernelGGL((surface_dense_var2_kernel<M, true, true>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);     \
-        else if (tsh) hipLaunchKernelGGL((surface_dense_var2_kernel<M, false, true>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);     \
-        else if (wl) hipLaunchKernelGGL((surface_dense_var2_kernel<M, true, false>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);      \
-        else hipLaunchKernelGGL((surface_dense_var2_kernel<M, false, false>), dim3((unsigned)grid), dim3(128), lds, st, p, vw.wl2);             \
-    }
-#define IVS_VAR_CASE(M, NAME)                                                  \
-    case M:                                                                    \
-        if (vw.need1) IVS_VAR_LAUNCH1(M)                                        \
-        if (vw.need2) IVS_VAR_LAUNCH2(M)                                        \
-        *name = NAME;                                                          \
-        break;
-    bool known = true;
-    switch (p.method) {
-        IVS_VAR_CASE(IVS_LINEAR, "surface_dense_var_kernel<linear>")
-        IVS_VAR_CASE(IVS_CUBIC, "surface_dense_var_kernel<cubic>")
-        IVS_VAR_CASE(IVS_CUBICSPLINE, "surface_dense_var_kernel<cubicspline>")
-        IVS_VAR_CASE(IVS_SLINEAR, "surface_dense_var_kernel<slinear>")
-        IVS_VAR_CASE(IVS_PCHIP, "surface_dense_var_kernel<pchip>")
-        IVS_VAR_CASE(IVS_AKIMA, "surface_dense_var_kernel<akima>")
-        default: known = false;
-    }
-#undef IVS_VAR_CASE
-#undef IVS_VAR_LAUNCH1
-#undef IVS_VAR_LAUNCH2
+    const bool known = with_method(p.method, DenseMethods{}, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        with_bool(wl, [&](auto w) {
+            with_bool(tsh, [&](auto t) {
+                constexpr bool W = decltype(w)::value, T = decltype(t)::value;
+                const size_t lds1 = dense_var_lds_bytes<1>(p.mT), lds2 = dense_var2_lds_bytes(p.mT);      // 40 KB: below the 64 KiB default limit
+                if (vw.need1) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, W, T>), grid_for(lds1), dim3(64), lds1, cx.st, p, vw.wl1);
+                if (vw.need2) hipLaunchKernelGGL((surface_dense_var2_kernel<M, W, T>), grid_for(lds2), dim3(128), lds2, cx.st, p, vw.wl2);
+            });
+        });
+    });
     if (!known) return 0;
-    const bool launched = hipGetLastError() == hipSuccess;
-    if (launched) launch_surface_generic<true>(p, cx);
-    return launched ? 1 : -1;
+    *family = "surface_dense_var_kernel";
+    if (hipGetLastError() != hipSuccess) return -1;
+    launch_redo_tail(p, cx, false);
+    return 1;
 }
 
 #endif  // IVS_DIAG_MINIMAL

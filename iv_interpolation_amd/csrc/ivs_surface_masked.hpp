@@ -198,28 +198,20 @@ namespace ivs {
 
 #ifndef IVS_DIAG_MINIMAL
 // Second pass behind the dense / row-pass kernel for uniform 64 x 16 batches: returns true when launched.
+using MaskedLerpMethods = Methods<IVS_LINEAR, IVS_SLINEAR, IVS_NEAREST, IVS_ZERO, IVS_FROM_DERIVATIVES>;      // surface_masked_kernel
+using MaskedSlopeMethods = Methods<IVS_CUBIC, IVS_CUBICSPLINE, IVS_QUADRATIC, IVS_PCHIP, IVS_AKIMA>;         // surface_masked_pass_kernel
 inline bool launch_surface_masked(const SurfaceParams& p, const LaunchCtx& cx) {
     if (p.k_off || p.nK != DK || p.nT != DT || p.mK > 64 || p.mT > D_MAX_MT) return false;
     if (p.t_stride != 0 || p.tq_stride != 0 || !p.tqs) return false;
     int64_t grid = (int64_t)cx.num_cu * 12;
     const int64_t work = (p.B + 63) / 64;
     if (grid > work) grid = work;
-    switch (p.method) {
-#define IVS_MASKED_CASE(KERNEL, LDS, M) case M: hipLaunchKernelGGL((KERNEL<M>), dim3((unsigned)grid), dim3(64), LDS, cx.st, p); break;
-        IVS_MASKED_CASE(surface_masked_kernel, masked_lds_bytes(), IVS_LINEAR)
-        IVS_MASKED_CASE(surface_masked_kernel, masked_lds_bytes(), IVS_SLINEAR)
-        IVS_MASKED_CASE(surface_masked_kernel, masked_lds_bytes(), IVS_NEAREST)
-        IVS_MASKED_CASE(surface_masked_kernel, masked_lds_bytes(), IVS_ZERO)
-        IVS_MASKED_CASE(surface_masked_kernel, masked_lds_bytes(), IVS_FROM_DERIVATIVES)
-        IVS_MASKED_CASE(surface_masked_pass_kernel, masked_pass_lds_bytes(), IVS_CUBIC)
-        IVS_MASKED_CASE(surface_masked_pass_kernel, masked_pass_lds_bytes(), IVS_CUBICSPLINE)
-        IVS_MASKED_CASE(surface_masked_pass_kernel, masked_pass_lds_bytes(), IVS_QUADRATIC)
-        IVS_MASKED_CASE(surface_masked_pass_kernel, masked_pass_lds_bytes(), IVS_PCHIP)
-        IVS_MASKED_CASE(surface_masked_pass_kernel, masked_pass_lds_bytes(), IVS_AKIMA)
-#undef IVS_MASKED_CASE
-        default: return false;
-    }
-    return true;
+    return with_method(p.method, MaskedLerpMethods{}, [&](auto m) {
+               hipLaunchKernelGGL((surface_masked_kernel<decltype(m)::value>), dim3((unsigned)grid), dim3(64), masked_lds_bytes(), cx.st, p);
+           }) ||
+           with_method(p.method, MaskedSlopeMethods{}, [&](auto m) {
+               hipLaunchKernelGGL((surface_masked_pass_kernel<decltype(m)::value>), dim3((unsigned)grid), dim3(64), masked_pass_lds_bytes(), cx.st, p);
+           });
 }
 #endif
 

@@ -751,19 +751,15 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
 #endif
 }
 
-// one launch; run-time-shape batches with the full 16 maturities take the NT16 instantiation
-template <int METHOD, int NKB, bool VAR>
-inline void launch_pass_nt(bool nt16, int64_t grid, size_t lds, hipStream_t st, const SurfaceParams& p, const VarList& list) {
-    if constexpr (VAR) {
-        if (nt16) { hipLaunchKernelGGL((surface_pass_kernel<METHOD, NKB, true, true, true>), dim3((unsigned)grid), dim3(64), lds, st, p, list); return; }
-    }
-    hipLaunchKernelGGL((surface_pass_kernel<METHOD, NKB, VAR, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, list);
-}
-// Dispatch of the row-pass kernels.  Returns 1 if dispatched (pass kernel(s) + filtered generic redo pass), 0 if the
-// call is outside their scope (see the head of this file), -1 on a launch error.
-inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, const char** name) {
+#ifdef IVS_DIAG_MINIMAL      // diagnostic builds (tools/pass_api.hip): the cubic kernels only
+using PassMethods = Methods<IVS_CUBIC>;
+#else
+using PassMethods = TableMethods;
+#endif
+// Dispatch of the row-pass kernels.  Returns 1 if dispatched (pass kernel(s) + redo tail), 0 if the call is outside
+// their scope (see the head of this file), -1 on a launch error.  *family: the kernel's name without its method.
+inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, const char** family) {
     SurfaceParams p = p_in;
-    hipStream_t st = cx.st;
     const bool lerp = p.method == IVS_LINEAR || p.method == IVS_SLINEAR || d_is_step(p.method);
     const bool local = d_is_local(p.method);
     if (!(p.method == IVS_CUBIC || p.method == IVS_CUBICSPLINE || p.method == IVS_QUADRATIC || lerp || local)) return 0;
@@ -777,80 +773,48 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
     const bool nt16 = p.nT == DT;       // run-time-shape kernels: maturity count fixed at compile time (NT16)
     if (!(fixed64 || nt16 ? launch_tq_or_zero_queue<false>(p, cx, tsh, fixed64)      // 16 maturities: the fixed-count tables
                           : launch_tq_or_zero_queue<true>(p, cx, tsh, fixed64))) return -1;
-    auto grid_for = [&](size_t lds, int64_t work, int wg_cap = 12) {
-        int per_cu = (int)((160 * 1024) / (((lds + 1279) / 1280) * 1280));     // LDS is granted in 1280-byte granules
-        per_cu = per_cu > wg_cap ? wg_cap : (per_cu < 1 ? 1 : per_cu);         // 3 wavefronts per SIMD (168 VGPRs)
+    // one launch of surface_pass_kernel<M, NKB, VAR> over `list`, at most `cap` workgroups per CU
+    auto launch = [&](auto m, auto nkb, auto var, int cap, const VarList& list) {
+        constexpr int M = decltype(m)::value, NKB = decltype(nkb)::value;
+        constexpr bool VAR = decltype(var)::value;
+        // the lerp methods carry no S plane and no tables; per-surface maturities: TT + W behind the planes
+        const size_t lds = pass_lds_bytes<NKB, d_is_local(M) ? 2 : (d_is_hermite(M) || d_is_quad(M)) ? 0 : 1>() + (tsh ? 0 : PASS_TQ_DOUBLES * 8);
+        // LDS is granted in 1280-byte granules; 3 wavefronts per SIMD (168 VGPRs), the run-time-maturity-count local rules 2
+        int per_cu = workgroups_per_cu(lds, (d_is_local(M) && VAR && !nt16) ? 8 : cap, 1280);
 #ifdef IVS_PASS_PER_CU
         per_cu = IVS_PASS_PER_CU;                                              // diagnostic builds (tools/pass_api.hip)
 #endif
-        const int64_t g = (int64_t)cx.num_cu * per_cu;
-        return g > work ? work : g;
+        int64_t grid = (int64_t)cx.num_cu * per_cu;
+        if (grid > p.B) grid = p.B;
+        if (!VAR) p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);
+        if constexpr (M == IVS_LINEAR) {
+            if (!tsh) {
+                hipLaunchKernelGGL((surface_pass_kernel<M, NKB, VAR, false>), dim3((unsigned)grid), dim3(64), lds, cx.st, p, list);
+                return;
+            }
+        }
+        // run-time-shape batches with the full 16 maturities take the NT16 instantiation
+        with_bool(VAR && nt16, [&](auto n) {
+            hipLaunchKernelGGL((surface_pass_kernel<M, NKB, VAR, true, VAR && decltype(n)::value>), dim3((unsigned)grid), dim3(64), lds, cx.st, p, list);
+        });
     };
-    const VarList none{nullptr, nullptr};
-    static const char* const names[2][10] = {
-        {"surface_pass_kernel<cubic>", "surface_pass_kernel<cubicspline>", "surface_pass_kernel<linear>", "surface_pass_kernel<slinear>",
-         "surface_pass_kernel<pchip>", "surface_pass_kernel<akima>", "surface_pass_kernel<nearest>", "surface_pass_kernel<zero>",
-         "surface_pass_kernel<from_derivatives>", "surface_pass_kernel<quadratic>"},
-        {"surface_pass_var_kernel<cubic>", "surface_pass_var_kernel<cubicspline>", "surface_pass_var_kernel<linear>",
-         "surface_pass_var_kernel<slinear>", "surface_pass_var_kernel<pchip>", "surface_pass_var_kernel<akima>",
-         "surface_pass_var_kernel<nearest>", "surface_pass_var_kernel<zero>", "surface_pass_var_kernel<from_derivatives>",
-         "surface_pass_var_kernel<quadratic>"}};
-    int mi = 0;
-    switch (p.method) {
-        case IVS_CUBIC: mi = 0; break; case IVS_CUBICSPLINE: mi = 1; break; case IVS_LINEAR: mi = 2; break; case IVS_SLINEAR: mi = 3; break;
-        case IVS_PCHIP: mi = 4; break; case IVS_AKIMA: mi = 5; break; case IVS_NEAREST: mi = 6; break; case IVS_ZERO: mi = 7; break;
-        case IVS_QUADRATIC: mi = 9; break;
-        default: mi = 8; break;
-    }
-    // one launch of surface_pass_kernel<method, NKB, VAR> over `list`; the lerp methods carry no S plane and no tables
-#ifdef IVS_DIAG_MINIMAL
-#define IVS_PASS_LAUNCH(NKB_, VAR_, CAP, LIST)                                                                                           \
-    {                                                                                                                                    \
-        const size_t lds = pass_lds_bytes<NKB_, 0>();                                                                                    \
-        const int64_t grid = grid_for(lds, p.B, CAP);                                                                                    \
-        if (!(VAR_)) p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);                                                          \
-        hipLaunchKernelGGL((surface_pass_kernel<IVS_CUBIC, NKB_, VAR_>), dim3((unsigned)grid), dim3(64), lds, st, p, LIST);              \
-    }
-#else
-#define IVS_PASS_LAUNCH(NKB_, VAR_, CAP, LIST)                                                                                           \
-    {                                                                                                                                    \
-        size_t lds = lerp ? pass_lds_bytes<NKB_, 1>() : (local ? pass_lds_bytes<NKB_, 2>() : pass_lds_bytes<NKB_, 0>());                 \
-        if (!tsh) lds += PASS_TQ_DOUBLES * 8;                                                                                            \
-        const int64_t grid = grid_for(lds, p.B, (local && (VAR_) && !nt16) ? 8 : (CAP));      /* 2 wavefronts per SIMD */                \
-        if (!(VAR_)) p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);                                                          \
-        if (!tsh) {                                                                                                                      \
-            hipLaunchKernelGGL((surface_pass_kernel<IVS_LINEAR, NKB_, VAR_, false>), dim3((unsigned)grid), dim3(64), lds, st, p, LIST);  \
-        } else                                                                                                                           \
-        switch (p.method) {                                                                                                              \
-            case IVS_CUBIC: launch_pass_nt<IVS_CUBIC, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                  \
-            case IVS_CUBICSPLINE: launch_pass_nt<IVS_CUBICSPLINE, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                      \
-            case IVS_LINEAR: launch_pass_nt<IVS_LINEAR, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                \
-            case IVS_NEAREST: launch_pass_nt<IVS_NEAREST, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                              \
-            case IVS_ZERO: launch_pass_nt<IVS_ZERO, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                    \
-            case IVS_FROM_DERIVATIVES: launch_pass_nt<IVS_FROM_DERIVATIVES, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;            \
-            case IVS_QUADRATIC: launch_pass_nt<IVS_QUADRATIC, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                          \
-            case IVS_PCHIP: launch_pass_nt<IVS_PCHIP, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                  \
-            case IVS_AKIMA: launch_pass_nt<IVS_AKIMA, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                  \
-            default: launch_pass_nt<IVS_SLINEAR, NKB_, VAR_>(nt16, grid, lds, st, p, LIST); break;                                       \
-        }                                                                                                                                \
-    }
-#endif
-    if (fixed64) {
-        IVS_PASS_LAUNCH(1, false, 12, none)
-        *name = names[0][mi];
-    } else {
-        VarWork vw;
-        if (!var_work_lists(p, cx, vw)) return -1;
-        if (vw.need1) IVS_PASS_LAUNCH(1, true, 12, vw.wl1)
-        if (vw.need2) IVS_PASS_LAUNCH(2, true, PASS_CAP2, vw.wl2)
-        *name = names[1][mi];
-    }
-#undef IVS_PASS_LAUNCH
-    if (hipGetLastError() != hipSuccess) return -1;
-#ifndef IVS_DIAG_MINIMAL
-    if (fixed64 && launch_surface_masked(p, cx) && p.redo) ++p.redo;   // tagged surfaces (missing quotes): the masked fast pass first ...
-#endif
-    launch_surface_generic<true>(p, cx);     // ... then the generic kernel for whatever is still tagged (cheap when nothing is)
+    bool ok = true;
+    const bool known = with_method(p.method, PassMethods{}, [&](auto m) {
+        using std::integral_constant;
+        if (fixed64) {
+            launch(m, integral_constant<int, 1>{}, std::false_type{}, 12, VarList{nullptr, nullptr});
+            *family = "surface_pass_kernel";
+        } else {
+            VarWork vw;
+            if (!(ok = var_work_lists(p, cx, vw))) return;
+            if (vw.need1) launch(m, integral_constant<int, 1>{}, std::true_type{}, 12, vw.wl1);
+            if (vw.need2) launch(m, integral_constant<int, 2>{}, std::true_type{}, PASS_CAP2, vw.wl2);
+            *family = "surface_pass_var_kernel";
+        }
+    });
+    if (!known) return 0;
+    if (!ok || hipGetLastError() != hipSuccess) return -1;
+    launch_redo_tail(p, cx, fixed64);
     return 1;
 }
 

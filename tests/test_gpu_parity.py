@@ -1077,3 +1077,136 @@ def test_missing_quotes_first_mode(method):
         # gap of four missing strikes the cancellation amplifies the last-bit differences of the secants (measured 1.3e-13)
         tol = (1e-12, 1e-13) if (method == "akima" and case == "sampled_clustered") else None
         close(got, ref, method, f"missing-quotes-first {case} {method} [{kern}]", tol)
+
+
+# ---- dispatch table: every branch of the surface launch layer, one tiny call (B = 3) per row ---------------------------------
+# (shape, method, variant, kernel): `kernel` is the ivs_last_kernel() string of this call as the launchers spelled it out case
+# by case BEFORE they moved to ivs_dispatch.hpp (which composes family<method>) -- not taken from the code under test.
+DISPATCH_TABLE = [
+    # uniform 64 x 16 -> 64 x 16, shared T / Tq: the row-pass kernels, the one-pass kernels behind the flag, the generic kernel
+    ("64x16", "linear", "", "surface_pass_kernel<linear>"),
+    ("64x16", "cubic", "", "surface_pass_kernel<cubic>"),
+    ("64x16", "cubicspline", "", "surface_pass_kernel<cubicspline>"),
+    ("64x16", "slinear", "", "surface_pass_kernel<slinear>"),
+    ("64x16", "nearest", "", "surface_pass_kernel<nearest>"),
+    ("64x16", "zero", "", "surface_pass_kernel<zero>"),
+    ("64x16", "pchip", "", "surface_pass_kernel<pchip>"),
+    ("64x16", "akima", "", "surface_pass_kernel<akima>"),
+    ("64x16", "from_derivatives", "", "surface_pass_kernel<from_derivatives>"),
+    ("64x16", "quadratic", "", "surface_pass_kernel<quadratic>"),
+    ("64x16", "linear", "one_pass", "surface_dense_kernel<linear>"),
+    ("64x16", "cubic", "one_pass", "surface_dense_kernel<cubic>"),
+    ("64x16", "cubicspline", "one_pass", "surface_dense_kernel<cubicspline>"),
+    ("64x16", "slinear", "one_pass", "surface_dense_kernel<slinear>"),
+    ("64x16", "pchip", "one_pass", "surface_dense_kernel<pchip>"),
+    ("64x16", "akima", "one_pass", "surface_dense_kernel<akima>"),
+    ("64x16", "nearest", "one_pass", "surface_generic_kernel"),
+    ("64x16", "cubic", "force_generic", "surface_generic_kernel"),
+    ("64x16", "pad", "", "surface_generic_kernel"),
+    ("64x16", "bfill", "", "surface_generic_kernel"),
+    # uniform 5 and 65 strikes x 4 maturities: both size classes of the run-time-shape kernels
+    ("5x4", "cubic", "", "surface_pass_var_kernel<cubic>"),
+    ("5x4", "linear", "", "surface_pass_var_kernel<linear>"),
+    ("5x4", "pchip", "", "surface_pass_var_kernel<pchip>"),
+    ("5x4", "quadratic", "", "surface_pass_var_kernel<quadratic>"),
+    ("5x4", "cubic", "one_pass", "surface_dense_var_kernel<cubic>"),
+    ("5x4", "linear", "one_pass", "surface_dense_var_kernel<linear>"),
+    ("5x4", "pchip", "one_pass", "surface_dense_var_kernel<pchip>"),
+    ("5x4", "quadratic", "one_pass", "surface_generic_kernel"),
+    ("65x4", "cubic", "", "surface_pass_var_kernel<cubic>"),
+    ("65x4", "linear", "", "surface_pass_var_kernel<linear>"),
+    ("65x4", "pchip", "", "surface_pass_var_kernel<pchip>"),
+    ("65x4", "quadratic", "", "surface_pass_var_kernel<quadratic>"),
+    ("65x4", "cubic", "one_pass", "surface_dense_var_kernel<cubic>"),
+    ("65x4", "linear", "one_pass", "surface_dense_var_kernel<linear>"),
+    ("65x4", "pchip", "one_pass", "surface_dense_var_kernel<pchip>"),
+    ("65x4", "quadratic", "one_pass", "surface_generic_kernel"),
+    # ragged, both size classes in one batch (5, 65 and 64 strikes): 16 maturities (NT16) and 5
+    ("ragged-nT16", "cubic", "", "surface_pass_var_kernel<cubic>"),
+    ("ragged-nT16", "pchip", "", "surface_pass_var_kernel<pchip>"),
+    ("ragged-nT5", "cubic", "", "surface_pass_var_kernel<cubic>"),
+    ("ragged-nT5", "pchip", "", "surface_pass_var_kernel<pchip>"),
+    # 65 output strikes: outside the row-pass scope
+    ("64x16-mK65", "cubic", "", "surface_dense_kernel<cubic>"),
+    ("64x16-mK65", "linear", "", "surface_dense_kernel<linear>"),
+    ("5x4-mK65", "cubic", "", "surface_dense_var_kernel<cubic>"),
+    ("5x4-mK65", "linear", "", "surface_dense_var_kernel<linear>"),
+    # per-surface T [B, nT] and Tq [B, mT]
+    ("64x16-perT", "linear", "", "surface_pass_kernel<linear>"),
+    ("64x16-perT", "cubic", "", "surface_dense_kernel<cubic>"),
+    ("65x4-perT", "cubic", "", "surface_dense_var_kernel<cubic>"),
+    # query maturities at D_WLDS_MAX_MT (weights in LDS) and one above (weights in registers)
+    ("64x16-mTmax", "cubic", "one_pass", "surface_dense_kernel<cubic>"),
+    ("64x16-mTmax+1", "cubic", "one_pass", "surface_dense_kernel<cubic>"),
+    # a missing quote in surface 1: the masked tail runs, the name stays that of the first kernel
+    ("64x16-nan", "cubic", "", "surface_pass_kernel<cubic>"),
+    ("64x16-nan", "linear", "", "surface_pass_kernel<linear>"),
+]
+
+
+def _wlds_max_mt():
+    import re
+    hdr = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "iv_interpolation_amd", "csrc", "ivs_surface_dense.hpp")
+    return int(re.search(r"constexpr int D_WLDS_MAX_MT = (\d+);", open(hdr).read()).group(1))
+
+
+_DISPATCH_INPUTS = {}
+
+
+def _dispatch_inputs(shape):
+    """(d, Kq, Tq, extra keyword arguments) of a DISPATCH_TABLE shape; built once per shape."""
+    from iv_interpolation_amd import synth
+    if shape in _DISPATCH_INPUTS:
+        return _DISPATCH_INPUTS[shape]
+    base, _, mod = shape.partition("-")
+    kw = {}
+    if base == "ragged":
+        nT = int(mod[2:])
+        counts = (5, 65, 64)
+        parts = [synth.numpy_batch(1, n, nT, seed=synth.BASE_SEED + 900 + n) for n in counts]
+        k_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        d = {"K": np.concatenate([p["K"][0] for p in parts]), "T": synth.tenors(nT),
+             "sigma": np.concatenate([p["sigma"][0].ravel() for p in parts])}
+        kw = {"k_off": k_off, "nK_max": max(counts), "n_maturities": nT}
+    else:
+        nK, nT = (int(v) for v in base.split("x"))
+        d = synth.numpy_batch(3, nK, nT, seed=synth.BASE_SEED + 900 + nK)
+    mK = 65 if mod == "mK65" else 64
+    mT = {"mTmax": _wlds_max_mt(), "mTmax+1": _wlds_max_mt() + 1}.get(mod, 16)
+    Kq, Tq = synth.query_grids(mK, mT, nT=nT)      # query maturities inside the hull of the nT tenors
+    if mod == "perT":
+        scale = 1.0 + 0.1 * np.arange(3)[:, None]
+        d["T"] = d["T"][None, :] * scale
+        Tq = Tq[None, :] * scale
+    if mod == "nan":
+        d["sigma"][1, 3, 7] = np.nan
+    _DISPATCH_INPUTS[shape] = (d, Kq, Tq, kw)
+    return _DISPATCH_INPUTS[shape]
+
+
+_DISPATCH_REF = {}
+
+
+def _dispatch_call(shape, method, variant):
+    """One row of DISPATCH_TABLE: (out, status, kernel name, oracle out); the oracle runs once per (shape, method)."""
+    import c_oracle
+    d, Kq, Tq, kw = _dispatch_inputs(shape)
+    if (shape, method) not in _DISPATCH_REF:
+        _DISPATCH_REF[shape, method] = c_oracle.load().surface_batch(d["K"], d["T"], d["sigma"], Kq, Tq, METHODS[method],
+                                                                     k_off=kw.get("k_off"))[0]
+    gkw = dict(kw, k_off=dev(kw["k_off"])) if kw else {}
+    if variant:
+        gkw[variant] = True
+    got, st, kern = _run(d, Kq, Tq, method, **gkw)
+    return got, st, kern, _DISPATCH_REF[shape, method]
+
+
+@pytest.mark.parametrize("shape,method,variant,kernel", DISPATCH_TABLE, ids=["-".join(filter(None, r[:3])) for r in DISPATCH_TABLE])
+def test_dispatch_table(shape, method, variant, kernel):
+    """Which kernel family and method a call reaches (the exact ivs_last_kernel() string), status 0 for every surface, and the
+    values against the C oracle, for every branch of the launch layer: method lists, shared / per-surface maturities,
+    weights in LDS or registers, NT16, the two size classes, the masked tail, the order of the fast paths."""
+    got, st, kern, ref = _dispatch_call(shape, method, variant)
+    assert kern == kernel
+    assert np.array_equal(st, np.zeros(3, np.int32))
+    close(got, ref, method, f"dispatch {shape} {method} {variant} [{kern}]")
