@@ -29,6 +29,7 @@ CANDLE_TABLE = "reconstructed_candles"
 SURFACE_TABLE = "iv_surfaces"
 SMILE_TABLE = "iv_smiles"
 ARBITRAGE_TABLE = "iv_arbitrage"
+VOLINDEX_TABLE = "iv_volindex"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -266,6 +267,32 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "arbitrage_free_snapshots": n_free,
                 "duration": duration}
 
+    def run_volindex(self) -> dict:
+        """Model-free volatility index: the snapshots of run_surfaces, then the strike integrals of
+        every tenor row and the 30-day constant-maturity index on the device, and one `iv_volindex` table per underlying
+        (rule M8: columns underlying, date, spot, vix_30d, flags_30d)."""
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, volindex_frame
+        print("\nVOLINDEX: MODEL-FREE VOLATILITY INDEX (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the volatility index"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_idx = 0
+        for res, rep in zip(results, builder.moments(results)):
+            table = volindex_frame([rep], [res])
+            self.store.write_table(VOLINDEX_TABLE, res.underlying, table)
+            n_rows += len(table)
+            finite = int(table["vix_30d"].notna().sum())
+            n_idx += finite
+            print(f"  {res.underlying}: {len(table)} snapshots, {finite} with a 30-day index")
+        duration = time.time() - start
+        print(f"\nVOLINDEX COMPLETE: {duration:.1f}s, underlyings {len(results)}, rows {n_rows:,}, indexed {n_idx:,}")
+        return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "indexed_snapshots": n_idx,
+                "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -299,7 +326,7 @@ class CompleteOptimizedPipeline:
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -340,6 +367,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_smiles()
             elif args.task == "arbitrage":
                 result = pipeline.run_arbitrage()
+            elif args.task == "volindex":
+                result = pipeline.run_volindex()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

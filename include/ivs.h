@@ -345,6 +345,58 @@ typedef struct ivs_arbitrage_args {
 int ivs_surface_arbitrage_f64(const ivs_arbitrage_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Model-free variance, skew, kurtosis and a constant-maturity volatility index off snapshot surfaces (DESIGN.md section
+ * 11, rules M1-M8; additive to ABI 5).  Per row (b, j) of `vol` the trapezoid over its valid strikes of g(x) Q / k^2, with
+ * Q the undiscounted out-of-the-money Black price at the node's vol and x = ln(k / F), F = spot exp(rate tau), and with
+ * the inputs of ivs_surface_arbitrage_f64:
+ *
+ *   vol [B][mT][mK], Kq / kq_stride, Tq / tq_stride, spot [B], rate      as for the arbitrage report; a stride is 0 (one
+ *                                      shared grid) or mK / mT (one grid per snapshot)
+ *   min_mass                           in [0, 1]: a row whose strikes cover less lognormal probability gets TRUNCATED
+ *                                      (0 = never)
+ *   horizons [nH] (HOST)               index horizons in years, finite and > 0; 0 <= nH <= 8; copied into the kernel
+ *                                      arguments by the call
+ *   raw [B][mT][4]                     the contracts L (log contract = index^2 tau), V, W, X (g = 2, 2(1 - x), 6x - 3x^2,
+ *                                      12x^2 - 4x^3)
+ *   stats [B][mT][4]                   mf_vol = sqrt(L / tau), bkm_vol = sqrt(var / tau), skew, kurt, with
+ *                                      mu = -V/2 - W/6 - X/24 and var = V - mu^2
+ *   mass [B][mT]                       the lognormal probability between the first and the last valid strike
+ *   flags [B][mT] (int32)              IVS_MM_*: DEAD = spot[b] or the tenor is not a finite positive number, fewer than 2
+ *                                      valid nodes, valid strikes not strictly ascending, or L <= 0 or var <= 0 (NaN in
+ *                                      every value of the row); ONE_SIDED = F outside the valid strikes; TRUNCATED = mass <
+ *                                      min_mass; HOLES = an invalid node between two valid ones was skipped
+ *   index [B][nH], index_flags [B][nH] (int32)    100 sqrt(L_h / h), L_h linear in tau between the first pair of consecutive
+ *                                      rows that are not DEAD and bracket h; the OR of the two rows' flags, or NaN and
+ *                                      NO_BRACKET; both NULL with nH == 0 (neither is touched then)
+ * Every element of every output is written, bitwise deterministically (plain stores, no atomics), in ONE launch.  mK >= 2,
+ * mT <= 512, nH <= 8 and B*mT < 2^31 are checked (IVS_ERANGE); B == 0 or mT == 0 is a no-op.  No workspace.
+ * snapshots_per_wg: how many consecutive snapshots one workgroup takes; 0 lets the call choose, 1..4 forces it
+ * (IVS_ERANGE outside).  The results do not depend on it, bit for bit.
+ */
+enum {
+    IVS_MM_ONE_SIDED  = 1,
+    IVS_MM_TRUNCATED  = 2,
+    IVS_MM_HOLES      = 4,
+    IVS_MM_DEAD       = 8,
+    IVS_MM_NO_BRACKET = 16
+};
+typedef struct ivs_moments_args {
+    const double* vol;
+    const double* Kq; int64_t kq_stride;
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate; double min_mass;
+    const double* horizons; /* host */ int32_t nH;
+    int32_t mK, mT; int64_t B;
+    double* raw;     /* [B][mT][4]  L, V, W, X */
+    double* stats;   /* [B][mT][4]  mf_vol, bkm_vol, skew, kurt */
+    double* mass;    /* [B][mT] */
+    int32_t* flags;  /* [B][mT] */
+    double* index; int32_t* index_flags; /* [B][nH]; both NULL with nH == 0: no M7 */
+    int32_t snapshots_per_wg; /* 0 = chosen by the call; 1..4 tuning / testing override, same bits */
+} ivs_moments_args;
+int ivs_surface_moments_f64(const ivs_moments_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -392,7 +444,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
- * ivs_surface_arbitrage_f64 call on this thread dispatched to (host string) */
+ * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 call on this thread dispatched to (host string) */
 const char* ivs_last_kernel(void);
 
 /*

@@ -16,6 +16,9 @@ ST_OK, ST_TOO_FEW_KNOTS, ST_BAD_SHAPE, ST_ILL_CONDITIONED = 0, 1, 2, 4
 SM_OK, SM_NO_CROSSING, SM_AMBIGUOUS, SM_DEAD = 0, 1, 2, 4      # IVS_SM_*: per-target flags of the smile points
 SM_MAX_TARGETS = 16
 AR_CALENDAR, AR_BUTTERFLY, AR_NO_STENCIL, AR_DEAD = 1, 2, 4, 8    # IVS_AR_*: per-node flags of the arbitrage report
+# IVS_MM_*: per-row flags of the model-free moments, NO_BRACKET on the index only
+MM_ONE_SIDED, MM_TRUNCATED, MM_HOLES, MM_DEAD, MM_NO_BRACKET = 1, 2, 4, 8, 16
+MM_MAX_HORIZONS = 8
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -104,6 +107,15 @@ class ArbitrageArgs(C.Structure):
                 ("flags", _p), ("counts", _p), ("worst", _p), ("local_vol", _p), ("density", _p)]
 
 
+class MomentsArgs(C.Structure):
+    """ivs_moments_args of include/ivs.h (field for field)."""
+    _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
+                ("spot", _p), ("rate", C.c_double), ("min_mass", C.c_double),
+                ("horizons", C.POINTER(C.c_double)), ("nH", _i32), ("mK", _i32), ("mT", _i32), ("B", _i64),
+                ("raw", _p), ("stats", _p), ("mass", _p), ("flags", _p), ("index", _p), ("index_flags", _p),
+                ("snapshots_per_wg", _i32)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -135,6 +147,7 @@ SIGNATURES = {
     "ivs_snapshot_assemble_f64": (C.c_int, [C.POINTER(SnapshotArgs), _p, _sz, _p]),
     "ivs_smile_delta_points_f64": (C.c_int, [C.POINTER(SmileArgs), _p, _sz, _p]),
     "ivs_surface_arbitrage_f64": (C.c_int, [C.POINTER(ArbitrageArgs), _p, _sz, _p]),
+    "ivs_surface_moments_f64": (C.c_int, [C.POINTER(MomentsArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }

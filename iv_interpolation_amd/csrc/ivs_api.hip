@@ -13,6 +13,7 @@
 #include "ivs_candles.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
+#include "ivs_moments.hpp"
 #include "ivs_smile.hpp"
 #include "ivs_snapshot.hpp"
 #include "ivs_surface_dense.hpp"
@@ -441,6 +442,51 @@ int ivs_surface_arbitrage_f64(const ivs_arbitrage_args* a, void* workspace, size
                        static_cast<hipStream_t>(stream), p);
     g_last_kernel = "surface_arbitrage_kernel";
     return check_launch("surface_arbitrage_kernel");
+}
+
+int ivs_surface_moments_f64(const ivs_moments_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_surface_moments_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->nH < 0 || a->kq_stride < 0 || a->tq_stride < 0)
+        return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->mK < 2) return fail(IVS_ERANGE, "%s: mK=%d < 2: a segment needs two nodes", fn, a->mK);
+    if (a->nH > ivs::MM_MAX_H) return fail(IVS_ERANGE, "%s: nH=%d outside [0,%d]", fn, a->nH, ivs::MM_MAX_H);
+    if (a->snapshots_per_wg < 0 || a->snapshots_per_wg > ivs::MM_MAX_SPW)
+        return fail(IVS_ERANGE, "%s: snapshots_per_wg=%d outside [0,%d]", fn, a->snapshots_per_wg, ivs::MM_MAX_SPW);
+    if (!(a->min_mass >= 0.0 && a->min_mass <= 1.0)) return fail(IVS_EINVAL, "%s: min_mass=%g outside [0,1]", fn, a->min_mass);
+    if (a->nH > 0 && !a->horizons) return fail(IVS_EINVAL, "%s: null horizons", fn);
+    for (int t = 0; t < a->nH; ++t)
+        if (!(a->horizons[t] > 0.0 && a->horizons[t] < __builtin_inf()))
+            return fail(IVS_EINVAL, "%s: horizon %d (%g) is not a finite positive number", fn, t, a->horizons[t]);
+    if (a->B == 0 || a->mT == 0) return IVS_OK;
+    if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->raw || !a->stats || !a->mass || !a->flags)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (a->nH > 0 && (!a->index || !a->index_flags)) return fail(IVS_EINVAL, "%s: null index / index_flags with nH=%d", fn, a->nH);
+    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
+        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (a->mT > ivs::MM_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d row slots per snapshot", fn, a->mT, ivs::MM_MAX_T);
+    ivs::MomParams p{};
+    p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
+    p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate; p.min_mass = a->min_mass;
+    for (int t = 0; t < a->nH; ++t) p.h[t] = a->horizons[t];
+    p.mK = a->mK; p.mT = a->mT; p.nH = a->nH; p.B = a->B;
+    p.raw = a->raw; p.stats = a->stats; p.mass = a->mass; p.flags = a->flags;
+    p.index = a->index; p.index_flags = a->index_flags;
+    // a workgroup takes as many whole snapshots as give each of its wavefronts a row
+    int spw = (ivs::MM_WAVES + a->mT - 1) / a->mT;
+    if (a->snapshots_per_wg > 0) spw = a->snapshots_per_wg;  // tuning / testing override
+    p.spw = spw;
+    const int64_t grid = (a->B + spw - 1) / spw;
+    const size_t lds = (size_t)spw * a->mT * sizeof(ivs::MomSlot);
+    hipLaunchKernelGGL(ivs::surface_moments_kernel, dim3((unsigned)grid), dim3(ivs::MM_WAVES * 64), lds,
+                       static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "surface_moments_kernel";
+    return check_launch("surface_moments_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

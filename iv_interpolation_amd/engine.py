@@ -304,6 +304,68 @@ def surface_arbitrage(vol, Kq, Tq, spot, rate: float = 0.0, *, local_vol: bool =
     return {k: out[k] for k in want}
 
 
+def surface_moments(vol, Kq, Tq, spot, rate: float = 0.0, *, horizons=(30.0 / 365.0,), min_mass: float = 0.99, out=None,
+                    stream=None, snapshots_per_wg: int = 0):
+    """Model-free variance, skew, kurtosis and a constant-maturity vol index of a batch of surfaces
+    (ivs_surface_moments_f64; rules M1-M7 of DESIGN.md section 11).  vol float64 [B,mT,mK] (the `out` of surface_batch);
+    Kq [mK] or [B,mK]; Tq [mT] or [B,mT]; spot [B]; all CUDA tensors; mK >= 2.  rate: the scalar r of the forward.
+    horizons: 0..8 index horizons in years (finite, > 0; ValueError otherwise); min_mass in [0, 1]: the lognormal
+    probability the strikes must cover before a row is flagged TRUNCATED (0 = never).
+    `out`: optional dict of preallocated outputs (keys raw, stats float64 [B,mT,4], mass float64 [B,mT], flags int32
+    [B,mT], index float64 [B,nH], index_flags int32 [B,nH]).
+    snapshots_per_wg: 0 lets the call choose how many snapshots share a workgroup; 1..4 forces it (tuning / testing; the
+    results are the same bit for bit).
+    Returns dict(raw, stats, mass, flags, index, index_flags) of device tensors (index / index_flags None without
+    horizons); raw = L, V, W, X; stats = mf_vol, bkm_vol, skew, kurt; flags are the _lib.MM_* bits."""
+    import ctypes
+    import math
+    hz = [float(h) for h in horizons]
+    if len(hz) > _lib.MM_MAX_HORIZONS:
+        raise ValueError(f"{len(hz)} horizons: at most {_lib.MM_MAX_HORIZONS} are supported")
+    if any(not (math.isfinite(h) and h > 0.0) for h in hz):
+        raise ValueError(f"horizons must be finite and > 0, got {hz!r}")
+    if not 0.0 <= float(min_mass) <= 1.0:
+        raise ValueError(f"min_mass {min_mass!r} is outside [0, 1]")
+    torch = require_device()
+    lib = _lib.load()
+    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if vol.dim() != 3:
+        raise ValueError("vol must be [B, mT, mK]")
+    B, mT, mK = vol.shape
+    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
+        raise ValueError("Kq must be [mK] or [B, mK]")
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+    nH = len(hz)
+    out = dict(out or {})
+    want = {"raw": ((B, mT, 4), torch.float64, True), "stats": ((B, mT, 4), torch.float64, True),
+            "mass": ((B, mT), torch.float64, True), "flags": ((B, mT), torch.int32, True),
+            "index": ((B, nH), torch.float64, nH > 0), "index_flags": ((B, nH), torch.int32, nH > 0)}
+    for k, (shape, dt, on) in want.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    hbuf = (ctypes.c_double * max(nH, 1))(*hz)
+    a = _lib.MomentsArgs()
+    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
+    a.Tq, a.tq_stride, a.spot, a.rate, a.min_mass = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate), float(min_mass)
+    a.horizons, a.nH = ctypes.cast(hbuf, ctypes.POINTER(ctypes.c_double)), nH
+    a.mK, a.mT, a.B = mK, mT, B
+    a.raw, a.stats, a.mass, a.flags = _ptr(out["raw"]), _ptr(out["stats"]), _ptr(out["mass"]), _ptr(out["flags"])
+    a.index, a.index_flags = _ptr(out["index"]), _ptr(out["index_flags"])
+    a.snapshots_per_wg = int(snapshots_per_wg)
+    rc = lib.ivs_surface_moments_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
+    _lib.check(rc, "ivs_surface_moments_f64")
+    return {k: out[k] for k in want}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -12,6 +12,8 @@ existing surface path (``engine.surface_batch``):
     pts, summ = smile_frame(q, res), smile_summary(q, res)
     a = b.arbitrage(res)                 # static-arbitrage flags, local vol, density: DESIGN.md section 10
     rep, lv = arbitrage_frame(a, res), local_vol_frame(a, res)
+    m = b.moments(res)                   # model-free variance, skew, kurtosis, vol index: DESIGN.md section 11
+    mom, vix = moments_frame(m, res), volindex_frame(m, res)
 
 The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
 NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
@@ -85,6 +87,27 @@ class ArbitrageReport:
     density: object                  # [B, mT, mK]
 
 
+DEFAULT_HORIZONS = (30.0 / 365.0,)   # rule M7: the 30-day index
+
+
+@dataclass
+class MomentReport:
+    """One underlying's model-free moments and vol index (rules M1-M7).  The arrays are device tensors with the HIP backend
+    (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tenors: np.ndarray               # [mT]
+    horizons: np.ndarray             # [nH] years
+    rate: float
+    min_mass: float
+    raw: object                      # [B, mT, 4]: L, V, W, X
+    stats: object                    # [B, mT, 4]: mf_vol, bkm_vol, skew, kurt
+    mass: object                     # [B, mT]
+    flags: object                    # [B, mT] int32, IVS_MM_*
+    index: object                    # [B, nH]
+    index_flags: object              # [B, nH] int32
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -116,6 +139,12 @@ class HipBackend:
         torch = engine.require_device()
         return engine.surface_arbitrage(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate,
                                         stream=self.stream)
+
+    def moments(self, vol, Kq, Tq, spot, rate, horizons, min_mass):
+        from . import engine
+        torch = engine.require_device()
+        return engine.surface_moments(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate,
+                                      horizons=horizons, min_mass=min_mass, stream=self.stream)
 
 
 def _host(a):
@@ -268,6 +297,25 @@ class SnapshotSurfaceBuilder:
                                            a["worst"], a["local_vol"], a["density"]))
         return reports
 
+    # ------------------------------------------------------------------ moments
+    def moments(self, results: Sequence[SnapshotSurfaces], rate: float = 0.0, horizons=None,
+                min_mass: float = 0.99) -> List[MomentReport]:
+        """Model-free variance, skew, kurtosis and the vol index of every surface of `results` (rules M1-M7): one
+        MomentReport per underlying, arrays on the device.  horizons: 1..8 index horizons in years (default
+        DEFAULT_HORIZONS); a horizon that is not finite and > 0, or a min_mass outside [0, 1], raises ValueError."""
+        hz = DEFAULT_HORIZONS if horizons is None else tuple(float(h) for h in horizons)
+        if not 1 <= len(hz) <= 8 or any(not (np.isfinite(h) and h > 0.0) for h in hz):
+            raise ValueError(f"horizons must be 1..8 finite positive numbers of years, got {hz!r}")
+        if not 0.0 <= float(min_mass) <= 1.0:
+            raise ValueError(f"min_mass {min_mass!r} is outside [0, 1]")
+        be = self._backend or HipBackend()
+        reports = []
+        for r in results:
+            m = be.moments(r.out, r.Kq, r.tenors, r.spot, float(rate), hz, float(min_mass))
+            reports.append(MomentReport(r.underlying, r.dates, r.tenors, np.asarray(hz, np.float64), float(rate), float(min_mass),
+                                        m["raw"], m["stats"], m["mass"], m["flags"], m["index"], m["index_flags"]))
+        return reports
+
     # ------------------------------------------------------------------ output
     @staticmethod
     def to_frame(results: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
@@ -299,6 +347,10 @@ class SnapshotSurfaceBuilder:
 
 def _pct(d: float) -> str:
     return f"{round(abs(d) * 100.0, 6):g}"
+
+
+def _days(h: float) -> str:
+    return f"{round(h * 365.0, 6):g}"
 
 
 def smile_frame(quotes: Sequence[SmileQuotes], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
@@ -408,3 +460,52 @@ def local_vol_frame(reports: Sequence[ArbitrageReport], snapshots: Sequence[Snap
                              "flags": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date", "tenor", "moneyness"], kind="stable").reset_index(drop=True)
+
+
+def moments_frame(reports: Sequence[MomentReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Rule M8: one row per (snapshot with quotes > 0, tenor), ordered by (underlying, date, tenor): columns underlying,
+    date, spot, tenor, mf_vol, bkm_vol, skew, kurt, mass, flags."""
+    parts = []
+    for m, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        st = _host(m.stats)[keep]
+        n, mT, _ = st.shape
+        parts.append(pd.DataFrame({
+            "underlying": m.underlying,
+            "date": m.dates[keep].repeat(mT),
+            "spot": np.repeat(_host(r.spot)[keep], mT),
+            "tenor": np.tile(m.tenors, n),
+            "mf_vol": st[:, :, 0].reshape(-1), "bkm_vol": st[:, :, 1].reshape(-1),
+            "skew": st[:, :, 2].reshape(-1), "kurt": st[:, :, 3].reshape(-1),
+            "mass": _host(m.mass)[keep].reshape(-1),
+            "flags": _host(m.flags)[keep].reshape(-1).astype(np.int32)}))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "tenor": f64, "mf_vol": f64, "bkm_vol": f64, "skew": f64, "kurt": f64, "mass": f64,
+                             "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
+
+
+def volindex_frame(reports: Sequence[MomentReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Rule M8: one row per snapshot with quotes > 0, ordered by (underlying, date): columns underlying, date, spot and, per
+    horizon in the order asked, vix_<days>d and flags_<days>d.  All reports must carry one and the same horizon list
+    (ValueError otherwise)."""
+    parts, names = [], None
+    if any(not np.array_equal(m.horizons, reports[0].horizons) for m in reports):
+        raise ValueError("volindex_frame: the reports were built with different horizon lists")
+    for m, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        ix, fx = _host(m.index)[keep], _host(m.index_flags)[keep]
+        cols = {"underlying": m.underlying, "date": m.dates[keep], "spot": _host(r.spot)[keep]}
+        for t, h in enumerate(m.horizons):
+            cols[f"vix_{_days(h)}d"] = ix[:, t]
+            cols[f"flags_{_days(h)}d"] = fx[:, t].astype(np.int32)
+        names = list(cols)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"),
+                             "spot": pd.Series(dtype=np.float64)})
+    df = pd.concat(parts, ignore_index=True)[names]
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
