@@ -1,6 +1,7 @@
 // N-minute candle aggregation (reference src/candle_reconstruction/core.py:68-88):
 // rows of one symbol sorted by timestamp; bucket = floor(ts / (N min)); open = first non-NaN, high = max,
-// low = min, close = last non-NaN, volume = Kahan sum in row order (pandas group_sum), count = rows in the bucket.
+// low = min, close = last non-NaN, volume = Kahan sum in row order (pandas group_sum; a NaN compensation is reset to 0, so
+// an infinite volume sums to that infinity), count = rows in the bucket.
 // One thread per input row; the thread that sits on the FIRST row of a bucket reduces the whole bucket (buckets hold
 // ~N rows) and writes the candle at that row's index; the other rows write count = 0.  Output is sparse (n rows),
 // the host keeps rows with count >= N.  HBM traffic: 48 B in + 60 B out per row, coalesced.
@@ -43,6 +44,7 @@ __global__ __launch_bounds__(256) void candle_kernel(CandleParams p) {
                 const double y = vv - comp;
                 const double t = sum + y;
                 comp = t - sum - y;
+                if (__builtin_isnan(comp)) comp = 0.0;                  // inf - inf after an infinite cell: reset, like pandas
                 sum = t;
             }
             ++count;

@@ -108,8 +108,8 @@ class OracleCandleBackend:
                 first = o[~np.isnan(o)]; last = c[~np.isnan(c)]
                 out_ts[a + i] = bucket[i]; cnt[a + i] = j - i
                 outs[0][a + i] = first[0] if first.size else np.nan
-                outs[1][a + i] = np.nanmax(h) if (~np.isnan(h)).any() else np.nan
-                outs[2][a + i] = np.nanmin(l) if (~np.isnan(l)).any() else np.nan
+                outs[1][a + i] = CO._first_extreme(h, True)
+                outs[2][a + i] = CO._first_extreme(l, False)
                 outs[3][a + i] = last[-1] if last.size else np.nan
                 outs[4][a + i] = CO._kahan_nansum(v)
         return [out_ts, *outs, cnt]

@@ -8,6 +8,8 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import candles_oracle as CO  # noqa: E402
+import candle_ref as CR  # noqa: E402
+from candle_cases import CASES as EDGE  # noqa: E402
 from golden_io import GOLDEN  # noqa: E402
 
 g = np.load(os.path.join(GOLDEN, "candles.npz"))
@@ -70,6 +72,70 @@ def test_hip_candles_batch_vs_oracle():
         assert np.array_equal(o["timestamp"].to_numpy().astype("datetime64[ns]").astype(np.int64), ref["timestamp"])
         for k in KEYS:
             assert np.array_equal(o[k].to_numpy(), ref[k], equal_nan=True)
+
+
+# ---- edge cases (candle_cases.py) against the operation itself in pandas (candle_ref.py): bit for bit, the sign of zero
+# included; every bucket (count >= 1) and the reference's rule for complete groups (count >= N)
+def _oracle_case(case, min_rows):
+    """candles_oracle.aggregate per series of a packed case, in the bucket layout of candle_ref.reference_case"""
+    off = case["series_off"]
+    keys = ("timestamp", "count") + CR.COLS
+    parts = {k: [] for k in keys}
+    for a, b in zip(off[:-1], off[1:]):
+        r = CO.aggregate(case["ts"][a:b], *[c[a:b] for c in case["cols"]], case["freq"], min_rows=min_rows)
+        if r is None:                                       # fewer rows than min_rows: no bucket can be complete
+            continue
+        for k in keys:
+            parts[k].append(r[k])
+    return {k: np.concatenate(v) if v else np.zeros(0, np.int64 if k in ("timestamp", "count") else np.float64)
+            for k, v in parts.items()}
+
+
+@pytest.mark.parametrize("name", list(EDGE))
+def test_oracle_equals_pandas_on_edge_cases(name):
+    case = EDGE[name]
+    for min_rows in (1, case["freq"]):
+        assert CR.mismatches(_oracle_case(case, min_rows), CR.reference_case(case, min_rows)) == [], (name, min_rows)
+
+
+@pytest.mark.parametrize("name", list(EDGE))
+def test_packed_model_equals_pandas_on_edge_cases(name):
+    """The row-by-row restatement of the packed operation with every rule on: the baseline of the wrong-variant check."""
+    case = EDGE[name]
+    out = CR.packed_model(case["ts"], case["cols"], case["series_off"], case["freq"])
+    for min_rows in (1, case["freq"]):
+        assert CR.mismatches(CR.sparse_to_buckets(out, min_rows), CR.reference_case(case, min_rows)) == [], (name, min_rows)
+
+
+@pytest.mark.parametrize("rule", ["series_check", "floor", "kahan", "comp_reset"])
+def test_edge_cases_separate_a_wrong_candle_kernel(rule):
+    """Each rule switched off in the packed model (no series check at the head, truncating division for the bucket, a
+    naive sum, no reset of a NaN compensation) must be caught by at least one case under the GPU test's comparison."""
+    caught = []
+    for name, case in EDGE.items():
+        out = CR.packed_model(case["ts"], case["cols"], case["series_off"], case["freq"], **{rule: False})
+        if any(CR.mismatches(CR.sparse_to_buckets(out, m), CR.reference_case(case, m)) for m in (1, case["freq"])):
+            caught.append(name)
+    assert caught, rule
+
+
+def test_pre_1970_buckets_floor_towards_minus_infinity():
+    r = CR.reference_case(EDGE["pre_1970_minutes"], 1)
+    assert list(r["timestamp"] // (5 * CR.MINUTE_NS)) == [-2, -1, 0] and list(r["count"]) == [2, 5, 3]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(EDGE))
+def test_hip_candles_equal_pandas_on_edge_cases(name):
+    import torch
+    from iv_interpolation_amd import engine
+    case = EDGE[name]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
+    out = engine.candle_aggregate(dev(case["ts"]), *[dev(c) for c in case["cols"]], dev(case["series_off"]), case["freq"])
+    out = [t.cpu().numpy() for t in out]
+    assert out[6].sum() == case["ts"].size                   # every row belongs to exactly one bucket
+    for min_rows in (1, case["freq"]):
+        assert CR.mismatches(CR.sparse_to_buckets(out, min_rows), CR.reference_case(case, min_rows)) == [], (name, min_rows)
 
 
 # ---- host-side API of the reference's module kept by the drop-in (core.py:108-300); expectations below were read off
