@@ -30,6 +30,7 @@ SURFACE_TABLE = "iv_surfaces"
 SMILE_TABLE = "iv_smiles"
 ARBITRAGE_TABLE = "iv_arbitrage"
 VOLINDEX_TABLE = "iv_volindex"
+SVI_TABLE = "iv_svi"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -293,6 +294,35 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "indexed_snapshots": n_idx,
                 "duration": duration}
 
+    def run_svi(self) -> dict:
+        """Raw SVI slices: the snapshots of run_surfaces, then one parametric fit per tenor row with
+        its butterfly check on the device, and one `iv_svi` table per underlying (rule V9: columns underlying, date, spot,
+        tenor, a, b, rho, m, sigma, rmse_vol, max_vol_err, g_min, flags)."""
+        from iv_interpolation_amd import _lib
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, svi_frame
+        print("\nSVI: RAW SVI SLICES WITH A BUTTERFLY CHECK (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the SVI slices"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_fit = n_bf = 0
+        for res, rep in zip(results, builder.svi(results)):
+            table = svi_frame([rep], [res])
+            self.store.write_table(SVI_TABLE, res.underlying, table)
+            n_rows += len(table)
+            fl = table["flags"].to_numpy()
+            fitted, bf = int(((fl & _lib.SV_DEAD) == 0).sum()), int(((fl & _lib.SV_BUTTERFLY) != 0).sum())
+            n_fit += fitted
+            n_bf += bf
+            print(f"  {res.underlying}: {len(table)} rows, {fitted} fitted, {bf} with butterfly arbitrage")
+        duration = time.time() - start
+        print(f"\nSVI COMPLETE: {duration:.1f}s, underlyings {len(results)}, rows {n_rows:,}, fitted {n_fit:,}, butterfly {n_bf:,}")
+        return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
+                "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -326,7 +356,7 @@ class CompleteOptimizedPipeline:
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -369,6 +399,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_arbitrage()
             elif args.task == "volindex":
                 result = pipeline.run_volindex()
+            elif args.task == "svi":
+                result = pipeline.run_svi()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -397,6 +397,60 @@ typedef struct ivs_moments_args {
 int ivs_surface_moments_f64(const ivs_moments_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Raw SVI slices off snapshot surfaces, with a butterfly check (rules V1-V9; additive to ABI 5).  Per
+ * row (b, j) of `vol` the least-squares fit of w(x) = a + b (rho (x - m) + sqrt((x - m)^2 + sigma^2)) to the total variances
+ * w = vol^2 tau at x = ln(k / spot) - rate tau of the row's valid nodes: a fixed number of rounds of an 8 x 8 grid search over
+ * (m, ln sigma), each candidate's (a, b, rho) from the exactly solved constrained linear problem (0 <= a <= max w,
+ * |rho| <= 1, b (1 + |rho|) <= 2).  Deterministic, no data-dependent loop counts.  With the inputs of
+ * ivs_surface_moments_f64:
+ *
+ *   vol [B][mT][mK], Kq / kq_stride, Tq / tq_stride, spot [B], rate      as for the moments; a stride is 0 (one shared grid)
+ *                                      or mK / mT (one grid per snapshot)
+ *   rounds                             rounds of the grid search; 0 = the default 16, 1..24 otherwise.  A round shrinks the
+ *                                      box to 2/7 of its width
+ *   params [B][mT][5]                  a, b, rho, m, sigma
+ *   fit [B][mT][4]                     rmse_w = sqrt(SSE / n) in total variance; rmse_vol and max_vol_err of the fitted vol
+ *                                      sqrt(w_fit / tau) against vol over the valid nodes; g_min = the minimum over the valid
+ *                                      nodes of Durrleman's g(x) = (1 - x w'/(2w))^2 - (w'^2/4)(1/w + 1/4) + w''/2 on the
+ *                                      fitted curve
+ *   flags [B][mT] (int32)              IVS_SV_*: DEAD (alone, NaN in every value of the row and in its `fitted` row) = spot[b]
+ *                                      or the tenor is not a finite positive number, fewer than 5 valid nodes, or valid
+ *                                      strikes not strictly ascending; HOLES = an invalid node between two valid ones was
+ *                                      skipped; BOUND = a constraint of the linear problem is active; EDGE = m or ln sigma
+ *                                      ended on a border of its domain ([first x, last x], [ln(X/256), ln(4X)], X = last x
+ *                                      - first x) or within 2^-20 of the domain's width of it; BUTTERFLY = g_min < 0; DEGENERATE = the fitted w is <= 0 at a valid node
+ *                                      (fitted vol 0 there, g_min NaN)
+ *   fitted [B][mT][mK] or NULL         the fitted vol at every node whose strike is a finite positive number, valid vol or
+ *                                      not (holes are filled); NaN elsewhere.  NULL: not computed, nothing is touched
+ * Every element of every requested output is written, bitwise deterministically (plain stores, no atomics), in ONE launch.
+ * 5 <= mK <= 1024, rounds, rows_per_wg and B*mT < 2^31 are checked (IVS_ERANGE); B == 0 or mT == 0 is a no-op.  No workspace.
+ * rows_per_wg: how many rows one workgroup takes, one per wavefront; 0 lets the call choose, 1..4 forces it.  The results
+ * do not depend on it, bit for bit.
+ */
+enum {
+    IVS_SV_BOUND      = 1,
+    IVS_SV_EDGE       = 2,
+    IVS_SV_HOLES      = 4,
+    IVS_SV_DEAD       = 8,
+    IVS_SV_BUTTERFLY  = 16,
+    IVS_SV_DEGENERATE = 32
+};
+typedef struct ivs_svi_args {
+    const double* vol;
+    const double* Kq; int64_t kq_stride;
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    int32_t mK, mT; int64_t B;
+    int32_t rounds;  /* 0 = 16 */
+    double* params;  /* [B][mT][5]  a, b, rho, m, sigma */
+    double* fit;     /* [B][mT][4]  rmse_w, rmse_vol, max_vol_err, g_min */
+    int32_t* flags;  /* [B][mT] */
+    double* fitted;  /* [B][mT][mK], may be NULL */
+    int32_t rows_per_wg; /* 0 = chosen by the call; 1..4 tuning / testing override, same bits */
+} ivs_svi_args;
+int ivs_svi_slices_f64(const ivs_svi_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -444,7 +498,8 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
- * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 call on this thread dispatched to (host string) */
+ * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 call on this thread dispatched to (host
+ * string) */
 const char* ivs_last_kernel(void);
 
 /*

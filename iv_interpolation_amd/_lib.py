@@ -19,6 +19,9 @@ AR_CALENDAR, AR_BUTTERFLY, AR_NO_STENCIL, AR_DEAD = 1, 2, 4, 8    # IVS_AR_*: pe
 # IVS_MM_*: per-row flags of the model-free moments, NO_BRACKET on the index only
 MM_ONE_SIDED, MM_TRUNCATED, MM_HOLES, MM_DEAD, MM_NO_BRACKET = 1, 2, 4, 8, 16
 MM_MAX_HORIZONS = 8
+# IVS_SV_*: per-row flags of the SVI slices
+SV_BOUND, SV_EDGE, SV_HOLES, SV_DEAD, SV_BUTTERFLY, SV_DEGENERATE = 1, 2, 4, 8, 16, 32
+SV_MAX_ROUNDS = 24
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -116,6 +119,13 @@ class MomentsArgs(C.Structure):
                 ("snapshots_per_wg", _i32)]
 
 
+class SviArgs(C.Structure):
+    """ivs_svi_args of include/ivs.h (field for field)."""
+    _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
+                ("spot", _p), ("rate", C.c_double), ("mK", _i32), ("mT", _i32), ("B", _i64), ("rounds", _i32),
+                ("params", _p), ("fit", _p), ("flags", _p), ("fitted", _p), ("rows_per_wg", _i32)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -148,6 +158,7 @@ SIGNATURES = {
     "ivs_smile_delta_points_f64": (C.c_int, [C.POINTER(SmileArgs), _p, _sz, _p]),
     "ivs_surface_arbitrage_f64": (C.c_int, [C.POINTER(ArbitrageArgs), _p, _sz, _p]),
     "ivs_surface_moments_f64": (C.c_int, [C.POINTER(MomentsArgs), _p, _sz, _p]),
+    "ivs_svi_slices_f64": (C.c_int, [C.POINTER(SviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }

@@ -16,6 +16,7 @@
 #include "ivs_moments.hpp"
 #include "ivs_smile.hpp"
 #include "ivs_snapshot.hpp"
+#include "ivs_svi.hpp"
 #include "ivs_surface_dense.hpp"
 #include "ivs_surface_dense_var2.hpp"
 #include "ivs_surface_pass.hpp"
@@ -487,6 +488,46 @@ int ivs_surface_moments_f64(const ivs_moments_args* a, void* workspace, size_t w
                        static_cast<hipStream_t>(stream), p);
     g_last_kernel = "surface_moments_kernel";
     return check_launch("surface_moments_kernel");
+}
+
+int ivs_svi_slices_f64(const ivs_svi_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_svi_slices_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->mK < 5) return fail(IVS_ERANGE, "%s: mK=%d < 5: five parameters need five nodes", fn, a->mK);
+    if (a->mK > ivs::SV_MAX_K) return fail(IVS_ERANGE, "%s: mK=%d > %d nodes of the LDS slot", fn, a->mK, ivs::SV_MAX_K);
+    if (a->rounds < 0 || a->rounds > ivs::SV_MAX_ROUNDS)
+        return fail(IVS_ERANGE, "%s: rounds=%d outside [0,%d]", fn, a->rounds, ivs::SV_MAX_ROUNDS);
+    if (a->rows_per_wg < 0 || a->rows_per_wg > ivs::SV_WAVES)
+        return fail(IVS_ERANGE, "%s: rows_per_wg=%d outside [0,%d]", fn, a->rows_per_wg, ivs::SV_WAVES);
+    if (a->B == 0 || a->mT == 0) return IVS_OK;
+    if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->params || !a->fit || !a->flags)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
+        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    ivs::SviParams p{};
+    p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
+    p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate;
+    p.mK = a->mK; p.mT = a->mT; p.rows = a->B * a->mT;
+    p.rounds = a->rounds == 0 ? ivs::SV_DEFAULT_ROUNDS : a->rounds;
+    p.params = a->params; p.fit = a->fit; p.flags = a->flags; p.fitted = a->fitted;
+    // one row per wavefront; a workgroup takes four rows once that still leaves every CU a workgroup, fewer below that
+    int dev, cus;
+    current_device(dev, cus);
+    int rpw = p.rows >= 4 * (int64_t)cus ? 4 : (p.rows >= 2 * (int64_t)cus ? 2 : 1);
+    if (a->rows_per_wg > 0) rpw = a->rows_per_wg;           // tuning / testing override
+    p.rpw = rpw;
+    const int64_t grid = (p.rows + rpw - 1) / rpw;
+    const size_t lds = (size_t)rpw * a->mK * 16;
+    hipLaunchKernelGGL(ivs::svi_slice_kernel, dim3((unsigned)grid), dim3(ivs::SV_WAVES * 64), lds,
+                       static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "svi_slice_kernel";
+    return check_launch("svi_slice_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

@@ -366,6 +366,57 @@ def surface_moments(vol, Kq, Tq, spot, rate: float = 0.0, *, horizons=(30.0 / 36
     return {k: out[k] for k in want}
 
 
+def svi_slices(vol, Kq, Tq, spot, rate: float = 0.0, *, rounds: int = 0, fitted: bool = False, out=None, stream=None,
+               rows_per_wg: int = 0):
+    """Raw SVI slices of a batch of surfaces with a butterfly check (ivs_svi_slices_f64; rules V1-V8 of DESIGN.md section
+    12).  vol float64 [B,mT,mK] (the `out` of surface_batch); Kq [mK] or [B,mK]; Tq [mT] or [B,mT]; spot [B]; all CUDA
+    tensors; 5 <= mK <= 1024.  rate: the scalar r of the forward.
+    rounds: rounds of the 8 x 8 grid search over (m, ln sigma); 0 = the default 16, 1..24 otherwise (ValueError outside).
+    fitted: True also returns the fitted vol at every strike (holes filled); False leaves it out (it is neither computed
+    nor written).
+    `out`: optional dict of preallocated outputs (keys params float64 [B,mT,5], fit float64 [B,mT,4], flags int32 [B,mT],
+    fitted float64 [B,mT,mK]).
+    rows_per_wg: 0 lets the call choose how many rows share a workgroup; 1..4 forces it (tuning / testing; the results are
+    the same bit for bit).
+    Returns dict(params, fit, flags, fitted) of device tensors (fitted None when left out); params = a, b, rho, m, sigma;
+    fit = rmse_w, rmse_vol, max_vol_err, g_min; flags are the _lib.SV_* bits."""
+    if not 0 <= int(rounds) <= _lib.SV_MAX_ROUNDS:
+        raise ValueError(f"rounds {rounds!r} is outside [0, {_lib.SV_MAX_ROUNDS}]")
+    torch = require_device()
+    lib = _lib.load()
+    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if vol.dim() != 3:
+        raise ValueError("vol must be [B, mT, mK]")
+    B, mT, mK = vol.shape
+    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
+        raise ValueError("Kq must be [mK] or [B, mK]")
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+    out = dict(out or {})
+    want = {"params": ((B, mT, 5), torch.float64, True), "fit": ((B, mT, 4), torch.float64, True),
+            "flags": ((B, mT), torch.int32, True), "fitted": ((B, mT, mK), torch.float64, bool(fitted))}
+    for k, (shape, dt, on) in want.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    a = _lib.SviArgs()
+    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
+    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.mK, a.mT, a.B, a.rounds = mK, mT, B, int(rounds)
+    a.params, a.fit, a.flags, a.fitted = _ptr(out["params"]), _ptr(out["fit"]), _ptr(out["flags"]), _ptr(out["fitted"])
+    a.rows_per_wg = int(rows_per_wg)
+    rc = lib.ivs_svi_slices_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
+    _lib.check(rc, "ivs_svi_slices_f64")
+    return {k: out[k] for k in want}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

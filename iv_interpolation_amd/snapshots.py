@@ -14,6 +14,8 @@ existing surface path (``engine.surface_batch``):
     rep, lv = arbitrage_frame(a, res), local_vol_frame(a, res)
     m = b.moments(res)                   # model-free variance, skew, kurtosis, vol index: DESIGN.md section 11
     mom, vix = moments_frame(m, res), volindex_frame(m, res)
+    v = b.svi(res)                       # raw SVI slice per tenor with a butterfly check: DESIGN.md section 12
+    fits = svi_frame(v, res)
 
 The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
 NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
@@ -108,6 +110,22 @@ class MomentReport:
     index_flags: object              # [B, nH] int32
 
 
+@dataclass
+class SviReport:
+    """One underlying's raw SVI slices (rules V1-V8).  The arrays are device tensors with the HIP backend (host arrays with
+    an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tenors: np.ndarray               # [mT]
+    moneyness: np.ndarray            # [mK]
+    rate: float
+    rounds: int                      # as asked: 0 = the default 16
+    params: object                   # [B, mT, 5]: a, b, rho, m, sigma
+    fit: object                      # [B, mT, 4]: rmse_w, rmse_vol, max_vol_err, g_min
+    flags: object                    # [B, mT] int32, IVS_SV_*
+    fitted: object                   # [B, mT, mK] fitted vols, or None
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -145,6 +163,12 @@ class HipBackend:
         torch = engine.require_device()
         return engine.surface_moments(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate,
                                       horizons=horizons, min_mass=min_mass, stream=self.stream)
+
+    def svi(self, vol, Kq, Tq, spot, rate, rounds, fitted):
+        from . import engine
+        torch = engine.require_device()
+        return engine.svi_slices(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, rounds=rounds,
+                                 fitted=fitted, stream=self.stream)
 
 
 def _host(a):
@@ -314,6 +338,21 @@ class SnapshotSurfaceBuilder:
             m = be.moments(r.out, r.Kq, r.tenors, r.spot, float(rate), hz, float(min_mass))
             reports.append(MomentReport(r.underlying, r.dates, r.tenors, np.asarray(hz, np.float64), float(rate), float(min_mass),
                                         m["raw"], m["stats"], m["mass"], m["flags"], m["index"], m["index_flags"]))
+        return reports
+
+    # ------------------------------------------------------------------ svi
+    def svi(self, results: Sequence[SnapshotSurfaces], rate: float = 0.0, rounds: int = 0, fitted: bool = False) -> List[SviReport]:
+        """Raw SVI slice of every tenor row of every surface of `results` (rules V1-V8): one SviReport per underlying,
+        arrays on the device.  rounds: 0 = the default 16, 1..24 otherwise (ValueError outside); fitted=True also keeps
+        the fitted vols [B, mT, mK]."""
+        if int(rounds) != rounds or not 0 <= int(rounds) <= 24:
+            raise ValueError(f"rounds must be 0 (the default) or 1..24, got {rounds!r}")
+        be = self._backend or HipBackend()
+        reports = []
+        for r in results:
+            v = be.svi(r.out, r.Kq, r.tenors, r.spot, float(rate), int(rounds), bool(fitted))
+            reports.append(SviReport(r.underlying, r.dates, r.tenors, r.moneyness, float(rate), int(rounds), v["params"], v["fit"],
+                                     v["flags"], v["fitted"]))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -509,3 +548,28 @@ def volindex_frame(reports: Sequence[MomentReport], snapshots: Sequence[Snapshot
                              "spot": pd.Series(dtype=np.float64)})
     df = pd.concat(parts, ignore_index=True)[names]
     return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def svi_frame(reports: Sequence[SviReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Rule V9: one row per (snapshot with quotes > 0, tenor), ordered by (underlying, date, tenor): columns underlying,
+    date, spot, tenor, a, b, rho, m, sigma, rmse_vol, max_vol_err, g_min, flags."""
+    parts = []
+    for v, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        pr, ft = _host(v.params)[keep], _host(v.fit)[keep]
+        n, mT, _ = pr.shape
+        cols = {"underlying": v.underlying, "date": v.dates[keep].repeat(mT), "spot": np.repeat(_host(r.spot)[keep], mT),
+                "tenor": np.tile(v.tenors, n)}
+        for q, name in enumerate(("a", "b", "rho", "m", "sigma")):
+            cols[name] = pr[:, :, q].reshape(-1)
+        for q, name in ((1, "rmse_vol"), (2, "max_vol_err"), (3, "g_min")):
+            cols[name] = ft[:, :, q].reshape(-1)
+        cols["flags"] = _host(v.flags)[keep].reshape(-1).astype(np.int32)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "tenor": f64, "a": f64, "b": f64, "rho": f64, "m": f64, "sigma": f64, "rmse_vol": f64,
+                             "max_vol_err": f64, "g_min": f64, "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
