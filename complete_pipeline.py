@@ -31,6 +31,7 @@ SMILE_TABLE = "iv_smiles"
 ARBITRAGE_TABLE = "iv_arbitrage"
 VOLINDEX_TABLE = "iv_volindex"
 SVI_TABLE = "iv_svi"
+DISTRIBUTION_TABLE = "iv_distribution"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -323,6 +324,36 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "duration": duration}
 
+    def run_distribution(self) -> dict:
+        """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
+        quantiles, level probabilities and tails of every tenor row on the device, and one `iv_distribution` table per
+        underlying (rule P9: columns underlying, date, spot, tenor, forward, q_1 ... q_99, below_80 ... below_120, tail_lo,
+        tail_hi, flags)."""
+        from iv_interpolation_amd import _lib
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, distribution_frame
+        print("\nDISTRIBUTION: RISK-NEUTRAL QUANTILES AND PROBABILITIES (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the distribution"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_live = n_amb = 0
+        for res, rep in zip(results, builder.distribution(results)):
+            table = distribution_frame([rep], [res])
+            self.store.write_table(DISTRIBUTION_TABLE, res.underlying, table)
+            n_rows += len(table)
+            fl = table["flags"].to_numpy()
+            live, amb = int(((fl & _lib.DS_DEAD) == 0).sum()), int(((fl & _lib.DS_AMBIGUOUS) != 0).sum())
+            n_live += live
+            n_amb += amb
+            print(f"  {res.underlying}: {len(table)} rows, {live} live, {amb} with a non-monotone CDF")
+        duration = time.time() - start
+        print(f"\nDISTRIBUTION COMPLETE: {duration:.1f}s, underlyings {len(results)}, rows {n_rows:,}, live {n_live:,}, ambiguous {n_amb:,}")
+        return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "live_rows": n_live, "ambiguous_rows": n_amb,
+                "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -356,7 +387,7 @@ class CompleteOptimizedPipeline:
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -401,6 +432,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_volindex()
             elif args.task == "svi":
                 result = pipeline.run_svi()
+            elif args.task == "distribution":
+                result = pipeline.run_distribution()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -451,6 +451,59 @@ typedef struct ivs_svi_args {
 int ivs_svi_slices_f64(const ivs_svi_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Risk-neutral distribution off the raw SVI slices: quantiles and probabilities (rules P1-P9; additive
+ * to ABI 5).  Per row (b, j) of `params` (the `params` of ivs_svi_slices_f64) the closed-form risk-neutral CDF of the slice
+ * w(x) = a + b (rho (x - m) + sqrt((x - m)^2 + sigma^2)), x = ln(K / F), F = spot exp(rate tau):
+ * L(x) = P(S_tau <= F e^x) = Phi(-d2) + phi(d2) theta'(x) and U = 1 - L = Phi(d2) - phi(d2) theta'(x), theta = sqrt(w),
+ * d2 = -x / theta - theta / 2.  A 64-point scan grid x_i = s0 y_i (s0 = theta(0), y_i = j (1 + j^2/64) / 8, j = i - 31.5,
+ * span +- 64.98 s0) brackets every target; 52 bisection steps invert it.  Deterministic, no data-dependent loop counts.
+ *
+ *   params [B][mT][5]                  a, b, rho, m, sigma.  A row is DEAD unless spot[b] and the tenor are finite and > 0, the
+ *                                      five parameters are finite, b >= 0, |rho| <= 1, sigma > 0 and a + b sigma sqrt(1 - rho^2)
+ *                                      > 0 (the DEAD rows of ivs_svi_slices_f64 carry NaN and so are DEAD here)
+ *   Tq, tq_stride / spot [B], rate     tenor grid of snapshot b at Tq + b*tq_stride (0 = one shared grid, else mT), S of
+ *                                      snapshot b, the scalar interest rate of the forward
+ *   probs [nP] (HOST)                  target probabilities, each strictly inside (0, 1); 1 <= nP <= 16; copied into the
+ *                                      kernel arguments by the call.  p <= 0.5 solves L(x) = p, p > 0.5 solves U(x) = 1 - p
+ *   levels [nL] (HOST)                 moneyness levels u (K = spot u), finite and > 0; 0 <= nL <= 16; copied likewise
+ *   max_tail                           in [0, 1]: the row gets TAILS when a tail of the scan grid exceeds it in magnitude
+ *   q_x, q_strike [B][mT][nP]          the quantile as x* = ln(K / F) and as the strike F exp(x*)
+ *   q_flags [B][mT][nP] (int32)        0, or IVS_DS_NO_BRACKET (no grid interval with h < 0 then h >= 0: NaN outputs),
+ *                                      IVS_DS_AMBIGUOUS (more than one: the first was used; the CDF is not monotone, a
+ *                                      butterfly arbitrage of the fit), IVS_DS_DEAD (the row is: NaN outputs)
+ *   p_below, p_above [B][mT][nL]       L and U at x = log(u) - rate tau; both NULL with nL == 0 (neither is touched then)
+ *   tails [B][mT][2]                   L(x_0) and U(x_63): the probability the scan grid leaves out on either side
+ *   flags [B][mT] (int32)              0, IVS_DS_TAILS (|L(x_0)| or |U(x_63)| > max_tail) or IVS_DS_DEAD (alone; NaN in every
+ *                                      value of the row)
+ * Every element of every output is written, bitwise deterministically (plain stores, no atomics), in ONE launch.  nP, nL,
+ * rows_per_wave and B*mT < 2^31 are checked (IVS_ERANGE); a probability outside (0, 1), a level that is not finite and > 0, a
+ * max_tail outside [0, 1] or a stride that is neither 0 nor mT is IVS_EINVAL; B == 0 or mT == 0 is a no-op.  No workspace, no
+ * allocation, no synchronisation (capturable).
+ * rows_per_wave: how many consecutive rows one wavefront takes (their rows x nP inversions share its 64 lanes); 0 lets the
+ * call choose by batch size, 1..64/nP forces it (IVS_ERANGE outside).  The results do not depend on it, bit for bit.
+ */
+enum {
+    IVS_DS_NO_BRACKET = 1,
+    IVS_DS_AMBIGUOUS  = 2,
+    IVS_DS_TAILS      = 4,
+    IVS_DS_DEAD       = 8
+};
+typedef struct ivs_distribution_args {
+    const double* params; /* [B][mT][5]  a, b, rho, m, sigma */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate; double max_tail;
+    const double* probs; /* host */ int32_t nP;
+    const double* levels; /* host */ int32_t nL;
+    int32_t mT; int64_t B;
+    double* q_x; double* q_strike; int32_t* q_flags; /* [B][mT][nP] */
+    double* p_below; double* p_above;                /* [B][mT][nL]; both NULL with nL == 0 */
+    double* tails;   /* [B][mT][2]  L(x_0), U(x_63) */
+    int32_t* flags;  /* [B][mT] */
+    int32_t rows_per_wave; /* 0 = chosen by the call; 1..64/nP = tuning / testing override, same bits */
+} ivs_distribution_args;
+int ivs_svi_distribution_f64(const ivs_distribution_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -498,8 +551,8 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
- * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 call on this thread dispatched to (host
- * string) */
+ * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
+ * dispatched to (host string) */
 const char* ivs_last_kernel(void);
 
 /*

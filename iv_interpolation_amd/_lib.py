@@ -22,6 +22,9 @@ MM_MAX_HORIZONS = 8
 # IVS_SV_*: per-row flags of the SVI slices
 SV_BOUND, SV_EDGE, SV_HOLES, SV_DEAD, SV_BUTTERFLY, SV_DEGENERATE = 1, 2, 4, 8, 16, 32
 SV_MAX_ROUNDS = 24
+# IVS_DS_*: flags of the risk-neutral distribution; NO_BRACKET / AMBIGUOUS per target, TAILS per row, DEAD on both
+DS_NO_BRACKET, DS_AMBIGUOUS, DS_TAILS, DS_DEAD = 1, 2, 4, 8
+DS_MAX_PROBS, DS_MAX_LEVELS = 16, 16
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -126,6 +129,15 @@ class SviArgs(C.Structure):
                 ("params", _p), ("fit", _p), ("flags", _p), ("fitted", _p), ("rows_per_wg", _i32)]
 
 
+class DistributionArgs(C.Structure):
+    """ivs_distribution_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double), ("max_tail", C.c_double),
+                ("probs", C.POINTER(C.c_double)), ("nP", _i32), ("levels", C.POINTER(C.c_double)), ("nL", _i32),
+                ("mT", _i32), ("B", _i64),
+                ("q_x", _p), ("q_strike", _p), ("q_flags", _p), ("p_below", _p), ("p_above", _p), ("tails", _p), ("flags", _p),
+                ("rows_per_wave", _i32)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -159,6 +171,7 @@ SIGNATURES = {
     "ivs_surface_arbitrage_f64": (C.c_int, [C.POINTER(ArbitrageArgs), _p, _sz, _p]),
     "ivs_surface_moments_f64": (C.c_int, [C.POINTER(MomentsArgs), _p, _sz, _p]),
     "ivs_svi_slices_f64": (C.c_int, [C.POINTER(SviArgs), _p, _sz, _p]),
+    "ivs_svi_distribution_f64": (C.c_int, [C.POINTER(DistributionArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }

@@ -11,6 +11,7 @@
 #include "ivs_arbitrage.hpp"
 #include "ivs_bridge.hpp"
 #include "ivs_candles.hpp"
+#include "ivs_distribution.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
 #include "ivs_moments.hpp"
@@ -528,6 +529,56 @@ int ivs_svi_slices_f64(const ivs_svi_args* a, void* workspace, size_t workspace_
                        static_cast<hipStream_t>(stream), p);
     g_last_kernel = "svi_slice_kernel";
     return check_launch("svi_slice_kernel");
+}
+
+int ivs_svi_distribution_f64(const ivs_distribution_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_svi_distribution_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->nP < 1 || a->nP > ivs::DS_MAX_P) return fail(IVS_ERANGE, "%s: nP=%d outside [1,%d]", fn, a->nP, ivs::DS_MAX_P);
+    if (a->nL < 0 || a->nL > ivs::DS_MAX_L) return fail(IVS_ERANGE, "%s: nL=%d outside [0,%d]", fn, a->nL, ivs::DS_MAX_L);
+    if (a->rows_per_wave < 0 || a->rows_per_wave > 64 / a->nP)
+        return fail(IVS_ERANGE, "%s: rows_per_wave=%d outside [0,%d] with nP=%d", fn, a->rows_per_wave, 64 / a->nP, a->nP);
+    if (!(a->max_tail >= 0.0 && a->max_tail <= 1.0)) return fail(IVS_EINVAL, "%s: max_tail=%g outside [0,1]", fn, a->max_tail);
+    if (!a->probs) return fail(IVS_EINVAL, "%s: null probs", fn);
+    if (a->nL > 0 && !a->levels) return fail(IVS_EINVAL, "%s: null levels", fn);
+    for (int t = 0; t < a->nP; ++t)
+        if (!(a->probs[t] > 0.0 && a->probs[t] < 1.0))
+            return fail(IVS_EINVAL, "%s: probability %d (%g) is not strictly inside (0, 1)", fn, t, a->probs[t]);
+    for (int l = 0; l < a->nL; ++l)
+        if (!(a->levels[l] > 0.0 && a->levels[l] < __builtin_inf()))
+            return fail(IVS_EINVAL, "%s: level %d (%g) is not a finite positive number", fn, l, a->levels[l]);
+    if (a->B == 0 || a->mT == 0) return IVS_OK;
+    if (!a->params || !a->Tq || !a->spot || !a->q_x || !a->q_strike || !a->q_flags || !a->tails || !a->flags)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (a->nL > 0 && (!a->p_below || !a->p_above)) return fail(IVS_EINVAL, "%s: null p_below / p_above with nL=%d", fn, a->nL);
+    if (a->tq_stride != 0 && a->tq_stride != a->mT) return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    ivs::DistParams p{};
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot;
+    p.tq_stride = a->tq_stride; p.rate = a->rate; p.max_tail = a->max_tail;
+    for (int t = 0; t < a->nP; ++t) p.probs[t] = a->probs[t];
+    for (int l = 0; l < a->nL; ++l) p.levels[l] = a->levels[l];
+    p.mT = a->mT; p.nP = a->nP; p.nL = a->nL; p.rows = a->B * a->mT;
+    p.q_x = a->q_x; p.q_strike = a->q_strike; p.q_flags = a->q_flags;
+    p.p_below = a->nL > 0 ? a->p_below : nullptr; p.p_above = a->nL > 0 ? a->p_above : nullptr;
+    p.tails = a->tails; p.flags = a->flags;
+    // rows per wavefront: fill the 64 lanes of the inversion phase, but keep ~16 wavefronts per CU while the batch is small
+    int dev, cus;
+    current_device(dev, cus);
+    int64_t group = p.rows / ((int64_t)cus * 16);
+    group = group < 1 ? 1 : (group > 64 / a->nP ? 64 / a->nP : group);
+    if (a->rows_per_wave > 0) group = a->rows_per_wave;     // tuning / testing override
+    p.group = (int32_t)group;
+    const int64_t waves = (p.rows + group - 1) / group;
+    hipLaunchKernelGGL(ivs::svi_distribution_kernel, dim3((unsigned)((waves + ivs::DS_WAVES - 1) / ivs::DS_WAVES)),
+                       dim3(ivs::DS_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "svi_distribution_kernel";
+    return check_launch("svi_distribution_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

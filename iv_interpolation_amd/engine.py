@@ -417,6 +417,83 @@ def svi_slices(vol, Kq, Tq, spot, rate: float = 0.0, *, rounds: int = 0, fitted:
     return {k: out[k] for k in want}
 
 
+DEFAULT_PROBS = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)      # rule P9: the probability cone
+DEFAULT_LEVELS = (0.8, 0.9, 1.0, 1.1, 1.2)                     # ... and the moneyness levels
+
+
+def distribution_targets(probs, levels, max_tail=1e-6):
+    """The host-side checks of DESIGN.md section 13: 1..16 probabilities strictly inside (0, 1), 0..16 finite positive
+    moneyness levels, max_tail in [0, 1]; ValueError otherwise.  Returns (probs, levels) as lists of floats."""
+    import math
+    probs, levels = [float(q) for q in probs], [float(u) for u in levels]
+    if not 1 <= len(probs) <= _lib.DS_MAX_PROBS:
+        raise ValueError(f"{len(probs)} probabilities: between 1 and {_lib.DS_MAX_PROBS} are supported")
+    if len(levels) > _lib.DS_MAX_LEVELS:
+        raise ValueError(f"{len(levels)} levels: at most {_lib.DS_MAX_LEVELS} are supported")
+    if any(not 0.0 < q < 1.0 for q in probs):
+        raise ValueError(f"probabilities must be strictly inside (0, 1), got {probs!r}")
+    if any(not (math.isfinite(u) and u > 0.0) for u in levels):
+        raise ValueError(f"levels must be finite and > 0, got {levels!r}")
+    if not 0.0 <= float(max_tail) <= 1.0:
+        raise ValueError(f"max_tail {max_tail!r} is outside [0, 1]")
+    return probs, levels
+
+
+def svi_distribution(params, Tq, spot, rate: float = 0.0, *, probs=DEFAULT_PROBS, levels=DEFAULT_LEVELS,
+                     max_tail: float = 1e-6, out=None, stream=None, rows_per_wave: int = 0):
+    """Risk-neutral quantiles and probabilities off a batch of raw SVI slices (ivs_svi_distribution_f64; rules P1-P8 of
+    DESIGN.md section 13).  params float64 [B,mT,5] (the `params` of svi_slices); Tq [mT] or [B,mT]; spot [B]; all CUDA
+    tensors.  rate: the scalar r of the forward.
+    probs: 1..16 probabilities strictly inside (0, 1); levels: 0..16 moneyness levels, finite and > 0; max_tail in [0, 1]:
+    the share of probability the scan grid may leave out on either side before the row is flagged TAILS (ValueError outside).
+    `out`: optional dict of preallocated outputs (keys q_x, q_strike float64 [B,mT,nP], q_flags int32 [B,mT,nP], p_below,
+    p_above float64 [B,mT,nL], tails float64 [B,mT,2], flags int32 [B,mT]).
+    rows_per_wave: 0 lets the call choose how many rows share a wavefront; 1..64 // nP forces it (tuning / testing; the
+    results are the same bit for bit).
+    Returns dict(q_x, q_strike, q_flags, p_below, p_above, tails, flags) of device tensors (p_below / p_above None without
+    levels); the flags are the _lib.DS_* bits."""
+    import ctypes
+    probs, levels = distribution_targets(probs, levels, max_tail)
+    torch = require_device()
+    lib = _lib.load()
+    params = _f64(torch, params, "params"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if params.dim() != 3 or params.shape[-1] != 5:
+        raise ValueError("params must be [B, mT, 5]")
+    B, mT, _ = params.shape
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+    nP, nL = len(probs), len(levels)
+    out = dict(out or {})
+    want = {"q_x": ((B, mT, nP), torch.float64, True), "q_strike": ((B, mT, nP), torch.float64, True),
+            "q_flags": ((B, mT, nP), torch.int32, True), "p_below": ((B, mT, nL), torch.float64, nL > 0),
+            "p_above": ((B, mT, nL), torch.float64, nL > 0), "tails": ((B, mT, 2), torch.float64, True),
+            "flags": ((B, mT), torch.int32, True)}
+    for k, (shape, dt, on) in want.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=params.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    pbuf, lbuf = (ctypes.c_double * nP)(*probs), (ctypes.c_double * max(nL, 1))(*levels)
+    a = _lib.DistributionArgs()
+    a.params, a.Tq, a.tq_stride = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT)
+    a.spot, a.rate, a.max_tail = _ptr(spot), float(rate), float(max_tail)
+    a.probs, a.nP = ctypes.cast(pbuf, ctypes.POINTER(ctypes.c_double)), nP
+    a.levels, a.nL = ctypes.cast(lbuf, ctypes.POINTER(ctypes.c_double)), nL
+    a.mT, a.B = mT, B
+    a.q_x, a.q_strike, a.q_flags = _ptr(out["q_x"]), _ptr(out["q_strike"]), _ptr(out["q_flags"])
+    a.p_below, a.p_above, a.tails, a.flags = _ptr(out["p_below"]), _ptr(out["p_above"]), _ptr(out["tails"]), _ptr(out["flags"])
+    a.rows_per_wave = int(rows_per_wave)
+    rc = lib.ivs_svi_distribution_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, params, Tq, spot, *out.values())
+    _lib.check(rc, "ivs_svi_distribution_f64")
+    return {k: out[k] for k in want}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -16,6 +16,8 @@ existing surface path (``engine.surface_batch``):
     mom, vix = moments_frame(m, res), volindex_frame(m, res)
     v = b.svi(res)                       # raw SVI slice per tenor with a butterfly check: DESIGN.md section 12
     fits = svi_frame(v, res)
+    d = b.distribution(res, v)           # risk-neutral quantiles and probabilities off the slices: DESIGN.md section 13
+    cone = distribution_frame(d, res)
 
 The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
 NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
@@ -31,6 +33,7 @@ import pandas as pd
 
 from . import synth
 from .engine import DEFAULT_DELTAS, delta_targets      # rule D3: 10d put, 25d put, ATM, 25d call, 10d call
+from .engine import DEFAULT_LEVELS, DEFAULT_PROBS, distribution_targets   # rule P9 and the host-side checks of section 13
 
 YEAR_NS = 365 * 86400 * 10**9       # S2: E_c = date + time_to_maturity x YEAR, YEAR = 365 days (the synthetic data's convention)
 MINUTE_NS = 60 * 10**9
@@ -126,6 +129,26 @@ class SviReport:
     fitted: object                   # [B, mT, mK] fitted vols, or None
 
 
+@dataclass
+class DistributionReport:
+    """One underlying's risk-neutral quantiles and probabilities (rules P1-P8).  The arrays are device tensors with the HIP
+    backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tenors: np.ndarray               # [mT]
+    probs: np.ndarray                # [nP] as asked
+    levels: np.ndarray               # [nL] as asked
+    rate: float
+    max_tail: float
+    q_x: object                      # [B, mT, nP] ln(K / F)
+    q_strike: object                 # [B, mT, nP]
+    q_flags: object                  # [B, mT, nP] int32, IVS_DS_*
+    p_below: object                  # [B, mT, nL], or None without levels
+    p_above: object                  # [B, mT, nL], or None without levels
+    tails: object                    # [B, mT, 2]: L(x_0), U(x_63)
+    flags: object                    # [B, mT] int32, IVS_DS_*
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -169,6 +192,12 @@ class HipBackend:
         torch = engine.require_device()
         return engine.svi_slices(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, rounds=rounds,
                                  fitted=fitted, stream=self.stream)
+
+    def distribution(self, params, Tq, spot, rate, probs, levels, max_tail):
+        from . import engine
+        torch = engine.require_device()
+        return engine.svi_distribution(params, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, probs=probs,
+                                       levels=levels, max_tail=max_tail, stream=self.stream)
 
 
 def _host(a):
@@ -353,6 +382,29 @@ class SnapshotSurfaceBuilder:
             v = be.svi(r.out, r.Kq, r.tenors, r.spot, float(rate), int(rounds), bool(fitted))
             reports.append(SviReport(r.underlying, r.dates, r.tenors, r.moneyness, float(rate), int(rounds), v["params"], v["fit"],
                                      v["flags"], v["fitted"]))
+        return reports
+
+    # ------------------------------------------------------------------ distribution
+    def distribution(self, results: Sequence[SnapshotSurfaces], svi_reports=None, rate: float = 0.0, probs=None, levels=None,
+                     max_tail: float = 1e-6, rounds: int = 0) -> List[DistributionReport]:
+        """Risk-neutral quantiles and probabilities of every tenor row of every surface of `results` (rules P1-P8): one
+        DistributionReport per underlying, arrays on the device.  svi_reports: the SviReports of svi(results, rate) to read
+        the slices from; None runs svi(results, rate, rounds) first.  probs: 1..16 probabilities strictly inside (0, 1)
+        (default DEFAULT_PROBS); levels: 0..16 finite positive moneyness levels (default DEFAULT_LEVELS); max_tail in
+        [0, 1]; ValueError outside."""
+        probs, levels = distribution_targets(DEFAULT_PROBS if probs is None else probs,
+                                             DEFAULT_LEVELS if levels is None else levels, max_tail)
+        if svi_reports is None:
+            svi_reports = self.svi(results, rate=rate, rounds=rounds)
+        if len(svi_reports) != len(results):
+            raise ValueError(f"{len(svi_reports)} SVI reports for {len(results)} surfaces")
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v in zip(results, svi_reports):
+            d = be.distribution(v.params, r.tenors, r.spot, float(rate), tuple(probs), tuple(levels), float(max_tail))
+            reports.append(DistributionReport(r.underlying, r.dates, r.tenors, np.asarray(probs, np.float64),
+                                              np.asarray(levels, np.float64), float(rate), float(max_tail), d["q_x"], d["q_strike"],
+                                              d["q_flags"], d["p_below"], d["p_above"], d["tails"], d["flags"]))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -572,4 +624,43 @@ def svi_frame(reports: Sequence[SviReport], snapshots: Sequence[SnapshotSurfaces
                              "tenor": f64, "a": f64, "b": f64, "rho": f64, "m": f64, "sigma": f64, "rmse_vol": f64,
                              "max_vol_err": f64, "g_min": f64, "flags": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
+
+
+def distribution_frame(reports: Sequence[DistributionReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """Rule P9: one row per (snapshot with quotes > 0, tenor), ordered by (underlying, date, tenor): columns underlying,
+    date, spot, tenor, forward, one strike column q_<pct> per probability in the order asked, one below_<pct> per level,
+    tail_lo, tail_hi, flags (the row's flag OR-ed with the OR of its targets' flags).  All reports must carry one and the
+    same probability and level lists, and no two probabilities or levels may round to the same percent label (6 decimals):
+    ValueError otherwise."""
+    parts, names = [], None
+    if reports:
+        labels = [f"q_{_pct(q)}" for q in reports[0].probs] + [f"below_{_pct(u)}" for u in reports[0].levels]
+        if len(set(labels)) != len(labels):
+            raise ValueError(f"distribution_frame: two probabilities or two levels share a column name: {labels}")
+    if any(not (np.array_equal(d.probs, reports[0].probs) and np.array_equal(d.levels, reports[0].levels)) for d in reports):
+        raise ValueError("distribution_frame: the reports were built with different probability or level lists")
+    for d, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        qk, qf, tl = _host(d.q_strike)[keep], _host(d.q_flags)[keep], _host(d.tails)[keep]
+        n, mT, _ = qk.shape
+        spot = np.repeat(_host(r.spot)[keep], mT)
+        tenor = np.tile(d.tenors, n)
+        cols = {"underlying": d.underlying, "date": d.dates[keep].repeat(mT), "spot": spot, "tenor": tenor,
+                "forward": spot * np.exp(d.rate * tenor)}
+        for t, q in enumerate(d.probs):
+            cols[f"q_{_pct(q)}"] = qk[:, :, t].reshape(-1)
+        if len(d.levels):
+            pb = _host(d.p_below)[keep]
+            for t, u in enumerate(d.levels):
+                cols[f"below_{_pct(u)}"] = pb[:, :, t].reshape(-1)
+        cols["tail_lo"], cols["tail_hi"] = tl[:, :, 0].reshape(-1), tl[:, :, 1].reshape(-1)
+        cols["flags"] = (_host(d.flags)[keep] | np.bitwise_or.reduce(qf, axis=-1)).reshape(-1).astype(np.int32)
+        names = list(cols)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "tenor": f64, "forward": f64, "tail_lo": f64, "tail_hi": f64, "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)[names]
     return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
