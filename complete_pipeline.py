@@ -32,6 +32,7 @@ ARBITRAGE_TABLE = "iv_arbitrage"
 VOLINDEX_TABLE = "iv_volindex"
 SVI_TABLE = "iv_svi"
 DISTRIBUTION_TABLE = "iv_distribution"
+CALENDAR_TABLE = "iv_calendar"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -354,6 +355,39 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "live_rows": n_live, "ambiguous_rows": n_amb,
                 "duration": duration}
 
+    def run_calendar(self) -> dict:
+        """Calendar report: the snapshots of run_surfaces and the slices of run_svi, then per snapshot
+        every pair of adjacent live slices compared on the device, and one `iv_calendar` table per underlying (columns
+        underlying, date, spot, tenor, next_tenor, d_min, x_min, d_atm, n_cross, x_first, x_last, flags)."""
+        from iv_interpolation_amd import _lib
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, calendar_frame
+        print("\nCALENDAR: CALENDAR CHECK BETWEEN THE SVI SLICES (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the calendar report"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_fit = n_bf = n_cal = n_wing = 0
+        for res, fit in zip(results, builder.svi(results)):
+            sv = _host_flags(fit.flags)[_host_flags(res.quotes) > 0]
+            n_fit += int(((sv & _lib.SV_DEAD) == 0).sum())
+            n_bf += int(((sv & _lib.SV_BUTTERFLY) != 0).sum())
+            table = calendar_frame(builder.calendar([res], [fit]), [res])
+            self.store.write_table(CALENDAR_TABLE, res.underlying, table)
+            n_rows += len(table)
+            fl = table["flags"].to_numpy()
+            cal = int(((fl & _lib.SC_CALENDAR) != 0).sum())
+            wing = int(((fl & (_lib.SC_WING_LEFT | _lib.SC_WING_RIGHT)) != 0).sum())
+            n_cal += cal
+            n_wing += wing
+            print(f"  {res.underlying}: {len(table)} pairs, {cal} crossing on the grid, {wing} crossing in a wing")
+        duration = time.time() - start
+        print(f"\nCALENDAR COMPLETE: {duration:.1f}s, underlyings {len(results)}, pairs {n_rows:,}, calendar {n_cal:,}, wing {n_wing:,}")
+        return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
+                "calendar_pairs": n_cal, "wing_pairs": n_wing, "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -385,9 +419,14 @@ class CompleteOptimizedPipeline:
         pass
 
 
+def _host_flags(a):
+    import numpy as np
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -434,6 +473,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_svi()
             elif args.task == "distribution":
                 result = pipeline.run_distribution()
+            elif args.task == "calendar":
+                result = pipeline.run_calendar()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -504,6 +504,89 @@ typedef struct ivs_distribution_args {
 int ivs_svi_distribution_f64(const ivs_distribution_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * SVI term structure: a calendar check between the slices of a snapshot and the surface at any (strike, expiry) (DESIGN.md
+ * section 14, rules T1-T4, C1-C6, E1-E6; additive to ABI 5).  Both read `params` [B][mT][5] (the `params` of
+ * ivs_svi_slices_f64), Tq / tq_stride (0 = one shared grid, else mT) and spot [B]; mT <= 64.  A row is live by the rule of
+ * ivs_svi_distribution_f64.  The live rows of a snapshot must have strictly ascending tenors; otherwise the snapshot is
+ * UNORDERED: every value of it is NaN and every flag of it is that flag alone.  w, w', w'' are those of the slice
+ * w(x) = a + b (rho (x - m) + sqrt((x - m)^2 + sigma^2)), x = ln(K / F).  Deterministic, no data-dependent loop counts.
+ *
+ * ivs_svi_calendar_f64: entry j of every output describes the pair (j, j'), j' the lowest live row above j.  A dead row gets
+ * IVS_SC_DEAD, the last live row IVS_SC_LAST, both NaN values and n_cross = 0.  d(x) = w_j'(x) - w_j(x) on the grid
+ * x_i = s0 y_i, s0 = sqrt(max(w_j(0), w_j'(0))), y_i = t (1 + t^2/1024) / 8, t = i - 31.5, i = 0..63 (span +- 7.75 s0), and
+ * at m_j and m_j' (points 64, 65):
+ *   d_min, x_min [B][mT]               the minimum of d over the 66 points (ties to the lowest index; a NaN compares as +inf)
+ *                                      and its x
+ *   d_atm [B][mT]                      d(0)
+ *   n_cross [B][mT] (int32)            grid cells i < 63 with (d(x_i) < 0) != (d(x_i+1) < 0)
+ *   x_cross [B][mT][2]                 the first and the last of those crossings, each by 52 bisection steps from its cell;
+ *                                      NaN without a crossing, twice the same with exactly one
+ *   flags [B][mT] (int32)              IVS_SC_CALENDAR = d_min < 0; IVS_SC_WING_LEFT = b'(1 - rho') < b(1 - rho) and
+ *                                      IVS_SC_WING_RIGHT = b'(1 + rho') < b(1 + rho): the later slice ends below the
+ *                                      earlier one beyond any grid; DEAD, LAST, UNORDERED alone
+ * rows_per_wave: how many consecutive rows one wavefront takes; 0 lets the call choose, 1..32 forces it (IVS_ERANGE
+ * outside).  The results do not depend on it, bit for bit.
+ *
+ * ivs_svi_eval_f64: Q queries (u, tau) per snapshot at u + b*q_stride, tau + b*q_stride (q_stride 0 = one shared list, else
+ * Q).  K = spot u (strike_mode 0) or K = u (strike_mode 1); F = spot exp(rate tau), x = log(K / spot) - rate tau,
+ * D = exp(-rate tau).  A query is IVS_SE_DEAD (NaN) unless u, tau and spot are finite and > 0 and the snapshot has a live row.
+ * lo = the last live row with tenor <= tau, hi = the first with tenor > tau; total variance, w' and w'' linear in the tenor
+ * between the two at fixed x; before the first live row that row scaled by tau / tenor (IVS_SE_SHORT), without a row above
+ * the last one likewise (IVS_SE_LONG).
+ *   w, vol [B][Q]                      W and sqrt(W / tau)
+ *   call, put [B][Q]                   D (F Phi(d1) - K Phi(d2)) and D (K Phi(-d2) - F Phi(-d1)), d1 = -x/theta + theta/2,
+ *                                      d2 = d1 - theta, theta = sqrt(W)
+ *   fwd_var [B][Q]                     V = (w_hi - w_lo) / (tenor_hi - tenor_lo) at fixed x; w / tenor under SHORT / LONG
+ *   g [B][Q]                           (1 - x W'/(2W))^2 - (W'^2/4)(1/W + 1/4) + W''/2
+ *   local_vol [B][Q]                   sqrt(V / g); NaN with IVS_SE_NEG_FWD (V < 0) or IVS_SE_NEG_G (g <= 0)
+ *   flags [B][Q] (int32)               IVS_SE_*; required.  Each of the seven value outputs may be NULL: it is then neither
+ *                                      computed nor written
+ * Every element of every requested output is written, bitwise deterministically (plain stores, no atomics), in ONE launch.
+ * IVS_EINVAL: null args or a null required pointer, a negative size, a stride that is neither 0 nor the full size, a
+ * strike_mode that is not 0 or 1; IVS_ERANGE: mT > 64, rows_per_wave outside 0..32, B*mT or B*Q >= 2^31; B == 0, mT == 0 or
+ * Q == 0 is a no-op.  No workspace, no allocation, no synchronisation (capturable).
+ */
+enum {
+    IVS_SC_CALENDAR   = 1,
+    IVS_SC_WING_LEFT  = 2,
+    IVS_SC_WING_RIGHT = 4,
+    IVS_SC_DEAD       = 8,
+    IVS_SC_LAST       = 16,
+    IVS_SC_UNORDERED  = 32
+};
+enum {
+    IVS_SE_SHORT      = 1,
+    IVS_SE_LONG       = 2,
+    IVS_SE_NEG_FWD    = 4,
+    IVS_SE_DEAD       = 8,
+    IVS_SE_NEG_G      = 16,
+    IVS_SE_UNORDERED  = 32
+};
+typedef struct ivs_calendar_args {
+    const double* params; /* [B][mT][5]  a, b, rho, m, sigma */
+    const double* Tq; int64_t tq_stride;
+    const double* spot;
+    int32_t mT; int64_t B;
+    double* d_min; double* x_min; double* d_atm; /* [B][mT] */
+    double* x_cross;  /* [B][mT][2] */
+    int32_t* n_cross; int32_t* flags; /* [B][mT] */
+    int32_t rows_per_wave; /* 0 = chosen by the call; 1..32 = tuning / testing override, same bits */
+} ivs_calendar_args;
+int ivs_svi_calendar_f64(const ivs_calendar_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+typedef struct ivs_eval_args {
+    const double* params; /* [B][mT][5]  a, b, rho, m, sigma */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* u; const double* tau; int64_t q_stride; /* [Q] (stride 0) or [B][Q] (stride Q) */
+    int32_t strike_mode; /* 0: K = spot u; 1: K = u */
+    int32_t mT; int64_t Q; int64_t B;
+    double* w; double* vol; double* call; double* put; double* fwd_var; double* g; double* local_vol; /* [B][Q], each may be NULL */
+    int32_t* flags;   /* [B][Q] */
+} ivs_eval_args;
+int ivs_svi_eval_f64(const ivs_eval_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -552,7 +635,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
- * dispatched to (host string) */
+ * dispatched to (host string); ivs_svi_calendar_f64 and ivs_svi_eval_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

@@ -25,6 +25,10 @@ SV_MAX_ROUNDS = 24
 # IVS_DS_*: flags of the risk-neutral distribution; NO_BRACKET / AMBIGUOUS per target, TAILS per row, DEAD on both
 DS_NO_BRACKET, DS_AMBIGUOUS, DS_TAILS, DS_DEAD = 1, 2, 4, 8
 DS_MAX_PROBS, DS_MAX_LEVELS = 16, 16
+# IVS_SC_*: per-pair flags of the SVI calendar report; IVS_SE_*: per-query flags of the SVI surface evaluation
+SC_CALENDAR, SC_WING_LEFT, SC_WING_RIGHT, SC_DEAD, SC_LAST, SC_UNORDERED = 1, 2, 4, 8, 16, 32
+SE_SHORT, SE_LONG, SE_NEG_FWD, SE_DEAD, SE_NEG_G, SE_UNORDERED = 1, 2, 4, 8, 16, 32
+ST_MAX_TENORS, SC_MAX_ROWS_PER_WAVE = 64, 32
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -138,6 +142,20 @@ class DistributionArgs(C.Structure):
                 ("rows_per_wave", _i32)]
 
 
+class CalendarArgs(C.Structure):
+    """ivs_calendar_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("mT", _i32), ("B", _i64),
+                ("d_min", _p), ("x_min", _p), ("d_atm", _p), ("x_cross", _p), ("n_cross", _p), ("flags", _p),
+                ("rows_per_wave", _i32)]
+
+
+class EvalArgs(C.Structure):
+    """ivs_eval_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("u", _p), ("tau", _p), ("q_stride", _i64), ("strike_mode", _i32), ("mT", _i32), ("Q", _i64), ("B", _i64),
+                ("w", _p), ("vol", _p), ("call", _p), ("put", _p), ("fwd_var", _p), ("g", _p), ("local_vol", _p), ("flags", _p)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -172,6 +190,8 @@ SIGNATURES = {
     "ivs_surface_moments_f64": (C.c_int, [C.POINTER(MomentsArgs), _p, _sz, _p]),
     "ivs_svi_slices_f64": (C.c_int, [C.POINTER(SviArgs), _p, _sz, _p]),
     "ivs_svi_distribution_f64": (C.c_int, [C.POINTER(DistributionArgs), _p, _sz, _p]),
+    "ivs_svi_calendar_f64": (C.c_int, [C.POINTER(CalendarArgs), _p, _sz, _p]),
+    "ivs_svi_eval_f64": (C.c_int, [C.POINTER(EvalArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }

@@ -12,6 +12,7 @@
 #include "ivs_bridge.hpp"
 #include "ivs_candles.hpp"
 #include "ivs_distribution.hpp"
+#include "ivs_svi_surface.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
 #include "ivs_moments.hpp"
@@ -579,6 +580,71 @@ int ivs_svi_distribution_f64(const ivs_distribution_args* a, void* workspace, si
                        dim3(ivs::DS_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
     g_last_kernel = "svi_distribution_kernel";
     return check_launch("svi_distribution_kernel");
+}
+
+int ivs_svi_calendar_f64(const ivs_calendar_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_svi_calendar_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one ballot", fn, a->mT, ivs::ST_MAX_T);
+    if (a->rows_per_wave < 0 || a->rows_per_wave > ivs::SC_MAX_GROUP)
+        return fail(IVS_ERANGE, "%s: rows_per_wave=%d outside [0,%d]", fn, a->rows_per_wave, ivs::SC_MAX_GROUP);
+    if (a->B == 0 || a->mT == 0) return IVS_OK;
+    if (!a->params || !a->Tq || !a->spot || !a->d_min || !a->x_min || !a->d_atm || !a->x_cross || !a->n_cross || !a->flags)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (a->tq_stride != 0 && a->tq_stride != a->mT) return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    ivs::CalParams p{};
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.tq_stride = a->tq_stride;
+    p.mT = a->mT; p.rows = a->B * a->mT;
+    p.d_min = a->d_min; p.x_min = a->x_min; p.d_atm = a->d_atm; p.x_cross = a->x_cross;
+    p.n_cross = a->n_cross; p.flags = a->flags;
+    // rows per wavefront: fill the 64 lanes of the inversion phase, but keep ~16 wavefronts per CU while the batch is small
+    int dev, cus;
+    current_device(dev, cus);
+    int64_t group = p.rows / ((int64_t)cus * 16);
+    group = group < 1 ? 1 : (group > ivs::SC_MAX_GROUP ? ivs::SC_MAX_GROUP : group);
+    if (a->rows_per_wave > 0) group = a->rows_per_wave;     // tuning / testing override
+    p.group = (int32_t)group;
+    const int64_t waves = (p.rows + group - 1) / group;
+    hipLaunchKernelGGL(ivs::svi_calendar_kernel, dim3((unsigned)((waves + ivs::SC_WAVES - 1) / ivs::SC_WAVES)),
+                       dim3(ivs::SC_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "svi_calendar_kernel";
+    return check_launch("svi_calendar_kernel");
+}
+
+int ivs_svi_eval_f64(const ivs_eval_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_svi_eval_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->Q < 0 || a->tq_stride < 0 || a->q_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->strike_mode != 0 && a->strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, a->strike_mode);
+    if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, a->mT, ivs::ST_MAX_T);
+    if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;
+    if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->flags) return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if ((a->tq_stride != 0 && a->tq_stride != a->mT) || (a->q_stride != 0 && a->q_stride != a->Q))
+        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (a->B > 0x7fffffffLL / a->Q)
+        return fail(IVS_ERANGE, "%s: %lld x %lld queries exceed one launch", fn, (long long)a->B, (long long)a->Q);
+    ivs::EvalParams p{};
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau;
+    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
+    p.mT = a->mT; p.strike_mode = a->strike_mode; p.Q = a->Q;
+    p.nqb = (int32_t)((a->Q + ivs::SE_BLOCK - 1) / ivs::SE_BLOCK);
+    p.w = a->w; p.vol = a->vol; p.call = a->call; p.put = a->put; p.fwd_var = a->fwd_var; p.g = a->g; p.local_vol = a->local_vol;
+    p.flags = a->flags;
+    const int64_t grid = a->B * p.nqb;                      // <= B * Q < 2^31
+    hipLaunchKernelGGL(ivs::svi_eval_kernel, dim3((unsigned)grid), dim3(ivs::SE_BLOCK), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "svi_eval_kernel";
+    return check_launch("svi_eval_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

@@ -494,6 +494,101 @@ def svi_distribution(params, Tq, spot, rate: float = 0.0, *, probs=DEFAULT_PROBS
     return {k: out[k] for k in want}
 
 
+def _svi_inputs(torch, params, Tq, spot):
+    """The shared input checks of the stages that read SVI slices: params [B,mT,5], Tq [mT] or [B,mT], spot [B]."""
+    params = _f64(torch, params, "params"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if params.dim() != 3 or params.shape[-1] != 5:
+        raise ValueError("params must be [B, mT, 5]")
+    B, mT, _ = params.shape
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+    if mT > _lib.ST_MAX_TENORS:
+        raise ValueError(f"mT = {mT}: at most {_lib.ST_MAX_TENORS} tenors per snapshot are supported")
+    return params, Tq, spot, B, mT
+
+
+def svi_calendar(params, Tq, spot, *, out=None, stream=None, rows_per_wave: int = 0):
+    """Calendar report between the raw SVI slices of every snapshot (ivs_svi_calendar_f64; rules T1-T4, C1-C6 of DESIGN.md
+    section 14).  params float64 [B,mT,5] (the `params` of svi_slices); Tq [mT] or [B,mT]; spot [B]; all CUDA tensors;
+    mT <= 64 (ValueError above).  Entry j describes the pair of row j and the next live row above it.
+    `out`: optional dict of preallocated outputs (keys d_min, x_min, d_atm float64 [B,mT], x_cross float64 [B,mT,2], n_cross,
+    flags int32 [B,mT]).
+    rows_per_wave: 0 lets the call choose how many rows share a wavefront; 1..32 forces it (tuning / testing; the results
+    are the same bit for bit).
+    Returns dict(d_min, x_min, d_atm, x_cross, n_cross, flags) of device tensors; the flags are the _lib.SC_* bits."""
+    torch = require_device()
+    lib = _lib.load()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    out = dict(out or {})
+    want = {"d_min": ((B, mT), torch.float64), "x_min": ((B, mT), torch.float64), "d_atm": ((B, mT), torch.float64),
+            "x_cross": ((B, mT, 2), torch.float64), "n_cross": ((B, mT), torch.int32), "flags": ((B, mT), torch.int32)}
+    for k, (shape, dt) in want.items():
+        t = out.get(k)
+        if t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=params.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    a = _lib.CalendarArgs()
+    a.params, a.Tq, a.tq_stride, a.spot = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot)
+    a.mT, a.B = mT, B
+    a.d_min, a.x_min, a.d_atm, a.x_cross = _ptr(out["d_min"]), _ptr(out["x_min"]), _ptr(out["d_atm"]), _ptr(out["x_cross"])
+    a.n_cross, a.flags = _ptr(out["n_cross"]), _ptr(out["flags"])
+    a.rows_per_wave = int(rows_per_wave)
+    rc = lib.ivs_svi_calendar_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, params, Tq, spot, *out.values())
+    _lib.check(rc, "ivs_svi_calendar_f64")
+    return {k: out[k] for k in want}
+
+
+EVAL_OUTPUTS = ("w", "vol", "call", "put", "fwd_var", "g", "local_vol")
+
+
+def svi_eval(params, Tq, spot, rate, u, tau, *, strike_mode: int = 0, want=EVAL_OUTPUTS, out=None, stream=None):
+    """The surface of the raw SVI slices at any (strike, expiry) (ivs_svi_eval_f64; rules T1-T3, E1-E6 of DESIGN.md section
+    14).  params float64 [B,mT,5]; Tq [mT] or [B,mT]; spot [B]; u, tau [Q] (one list for all snapshots) or [B,Q], both of one
+    shape; all CUDA tensors; mT <= 64.  rate: the scalar r of the forward and the discount factor.
+    strike_mode: 0 = u is a moneyness level (K = spot u), 1 = u is the strike (ValueError otherwise).
+    want: which of EVAL_OUTPUTS to compute; one left out is neither computed nor written (None in the result).
+    `out`: optional dict of preallocated outputs (float64 [B,Q] per value, flags int32 [B,Q]).
+    Returns dict(w, vol, call, put, fwd_var, g, local_vol, flags) of device tensors; the flags are the _lib.SE_* bits."""
+    if strike_mode not in (0, 1):
+        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    want = tuple(want)
+    if any(k not in EVAL_OUTPUTS for k in want):
+        raise ValueError(f"want must name outputs among {EVAL_OUTPUTS}, got {want!r}")
+    torch = require_device()
+    lib = _lib.load()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    u = _f64(torch, u, "u"); tau = _f64(torch, tau, "tau")
+    if u.dim() not in (1, 2) or u.shape != tau.shape or (u.dim() == 2 and u.shape[0] != B):
+        raise ValueError("u and tau must both be [Q] or both [B, Q]")
+    Q = u.shape[-1]
+    out = dict(out or {})
+    shapes = {k: ((B, Q), torch.float64, k in want) for k in EVAL_OUTPUTS}
+    shapes["flags"] = ((B, Q), torch.int32, True)
+    for k, (shape, dt, on) in shapes.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=params.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    a = _lib.EvalArgs()
+    a.params, a.Tq, a.tq_stride, a.spot, a.rate = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.u, a.tau, a.q_stride, a.strike_mode = _ptr(u), _ptr(tau), (0 if u.dim() == 1 else Q), int(strike_mode)
+    a.mT, a.Q, a.B = mT, Q, B
+    for k in EVAL_OUTPUTS:
+        setattr(a, k, _ptr(out[k]))
+    a.flags = _ptr(out["flags"])
+    rc = lib.ivs_svi_eval_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, params, Tq, spot, u, tau, *out.values())
+    _lib.check(rc, "ivs_svi_eval_f64")
+    return {k: out[k] for k in shapes}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

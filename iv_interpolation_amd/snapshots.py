@@ -18,6 +18,10 @@ existing surface path (``engine.surface_batch``):
     fits = svi_frame(v, res)
     d = b.distribution(res, v)           # risk-neutral quantiles and probabilities off the slices: DESIGN.md section 13
     cone = distribution_frame(d, res)
+    cal = b.calendar(res, v)             # do the slices of a snapshot cross between tenors: DESIGN.md section 14
+    pairs = calendar_frame(cal, res)
+    marks = b.price(res, book, v)        # vol, call, put, forward variance, local vol of a book of (strike, expiry)
+    priced = price_frame(marks, res)
 
 The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
 NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
@@ -149,6 +153,42 @@ class DistributionReport:
     flags: object                    # [B, mT] int32, IVS_DS_*
 
 
+@dataclass
+class CalendarReport:
+    """One underlying's calendar report between its SVI slices (rules T1-T4, C1-C6).  Entry j describes the pair of row j and
+    the next live row above it.  The arrays are device tensors with the HIP backend (host arrays with an injected CPU
+    backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tenors: np.ndarray               # [mT]
+    d_min: object                    # [B, mT] the minimum of w_j' - w_j over the grid and the two vertices
+    x_min: object                    # [B, mT] where, as ln(K / F)
+    d_atm: object                    # [B, mT] at the forward
+    x_cross: object                  # [B, mT, 2] the first and the last crossing
+    n_cross: object                  # [B, mT] int32
+    flags: object                    # [B, mT] int32, IVS_SC_*
+
+
+@dataclass
+class PriceReport:
+    """One underlying's book of (strike, expiry) marked to every snapshot (rules E1-E6).  The value arrays are device tensors
+    with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    strikes: np.ndarray              # [Q]
+    expiries: pd.DatetimeIndex       # [Q]
+    tau: np.ndarray                  # [B, Q] years from the snapshot to the expiry (<= 0: expired, DEAD)
+    rate: float
+    w: object                        # [B, Q] total variance
+    vol: object                      # [B, Q]
+    call: object                     # [B, Q]
+    put: object                      # [B, Q]
+    fwd_var: object                  # [B, Q]
+    g: object                        # [B, Q]
+    local_vol: object                # [B, Q]
+    flags: object                    # [B, Q] int32, IVS_SE_*
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -198,6 +238,17 @@ class HipBackend:
         torch = engine.require_device()
         return engine.svi_distribution(params, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, probs=probs,
                                        levels=levels, max_tail=max_tail, stream=self.stream)
+
+    def calendar(self, params, Tq, spot):
+        from . import engine
+        torch = engine.require_device()
+        return engine.svi_calendar(params, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, stream=self.stream)
+
+    def evaluate(self, params, Tq, spot, rate, u, tau, strike_mode):
+        from . import engine
+        torch = engine.require_device()
+        d = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()  # noqa: E731
+        return engine.svi_eval(params, d(Tq), spot, rate, d(u), d(tau), strike_mode=strike_mode, stream=self.stream)
 
 
 def _host(a):
@@ -405,6 +456,57 @@ class SnapshotSurfaceBuilder:
             reports.append(DistributionReport(r.underlying, r.dates, r.tenors, np.asarray(probs, np.float64),
                                               np.asarray(levels, np.float64), float(rate), float(max_tail), d["q_x"], d["q_strike"],
                                               d["q_flags"], d["p_below"], d["p_above"], d["tails"], d["flags"]))
+        return reports
+
+    # ------------------------------------------------------------------ calendar
+    def _slices(self, results, svi_reports, rate, rounds):
+        if svi_reports is None:
+            svi_reports = self.svi(results, rate=rate, rounds=rounds)
+        if len(svi_reports) != len(results):
+            raise ValueError(f"{len(svi_reports)} SVI reports for {len(results)} surfaces")
+        return svi_reports
+
+    def calendar(self, results: Sequence[SnapshotSurfaces], svi_reports=None, rate: float = 0.0, rounds: int = 0) -> List[CalendarReport]:
+        """Calendar report between the SVI slices of every surface of `results` (rules T1-T4, C1-C6): one CalendarReport per
+        underlying, arrays on the device.  svi_reports: the SviReports of svi(results, rate) to read the slices from; None
+        runs svi(results, rate, rounds) first."""
+        svi_reports = self._slices(results, svi_reports, rate, rounds)
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v in zip(results, svi_reports):
+            c = be.calendar(v.params, r.tenors, r.spot)
+            reports.append(CalendarReport(r.underlying, r.dates, r.tenors, c["d_min"], c["x_min"], c["d_atm"], c["x_cross"],
+                                          c["n_cross"], c["flags"]))
+        return reports
+
+    # ------------------------------------------------------------------ price
+    def price(self, results: Sequence[SnapshotSurfaces], book: pd.DataFrame, svi_reports=None, rate: float = 0.0,
+              rounds: int = 0) -> List[PriceReport]:
+        """Marks a book of options to every surface of `results` (rules E1-E6): one PriceReport per underlying.  book: a
+        frame with the columns strike and expiry (timestamps; naive ones are read in the time zone of the snapshots); the
+        time to expiry is (expiry - snapshot date) / YEAR per snapshot, and an expired option is DEAD.  svi_reports as for
+        calendar()."""
+        for c in ("strike", "expiry"):
+            if c not in book.columns:
+                raise KeyError(c)
+        svi_reports = self._slices(results, svi_reports, rate, rounds)
+        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
+        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v in zip(results, svi_reports):
+            e = expiry
+            if e.tz is None and r.dates.tz is not None:
+                e = e.tz_localize(r.dates.tz)
+            elif e.tz is not None and r.dates.tz is None:
+                e = e.tz_convert("UTC").tz_localize(None)
+            e_ns, d_ns = e.as_unit("ns").asi8, r.dates.as_unit("ns").asi8
+            tau = (e_ns[None, :] - d_ns[:, None]).astype(np.float64) / float(YEAR_NS)
+            tau[:, np.asarray(e.isna())] = np.nan
+            u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
+            q = be.evaluate(v.params, r.tenors, r.spot, float(rate), u, tau, 1)
+            reports.append(PriceReport(r.underlying, r.dates, strikes, expiry, tau, float(rate), q["w"], q["vol"], q["call"], q["put"],
+                                       q["fwd_var"], q["g"], q["local_vol"], q["flags"]))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -664,3 +766,58 @@ def distribution_frame(reports: Sequence[DistributionReport], snapshots: Sequenc
                              "tenor": f64, "forward": f64, "tail_lo": f64, "tail_hi": f64, "flags": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)[names]
     return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
+
+
+SC_NO_PAIR = 8 | 16 | 32             # IVS_SC_DEAD | IVS_SC_LAST | IVS_SC_UNORDERED: entry j describes no pair
+
+
+def calendar_frame(reports: Sequence[CalendarReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per (snapshot with quotes > 0, live pair), ordered by (underlying, date, tenor): columns underlying, date, spot,
+    tenor, next_tenor (the pair's two tenors), d_min, x_min, d_atm, n_cross, x_first, x_last, flags."""
+    parts = []
+    for c, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        fl = _host(c.flags)[keep].astype(np.int32)
+        n, mT = fl.shape
+        nxt = np.full((n, mT), np.nan)                                       # the tenor of the lowest live row above j
+        last = np.full(n, np.nan)
+        for j in range(mT - 1, -1, -1):
+            nxt[:, j] = last
+            last = np.where((fl[:, j] & 8) == 0, c.tenors[j], last)
+        s, j = np.nonzero((fl & SC_NO_PAIR) == 0)
+        xc = _host(c.x_cross)[keep]
+        parts.append(pd.DataFrame({
+            "underlying": c.underlying, "date": c.dates[keep][s], "spot": _host(r.spot)[keep][s],
+            "tenor": c.tenors[j], "next_tenor": nxt[s, j],
+            "d_min": _host(c.d_min)[keep][s, j], "x_min": _host(c.x_min)[keep][s, j], "d_atm": _host(c.d_atm)[keep][s, j],
+            "n_cross": _host(c.n_cross)[keep][s, j].astype(np.int32), "x_first": xc[s, j, 0], "x_last": xc[s, j, 1],
+            "flags": fl[s, j]}))
+    if not parts:
+        f64, i32 = pd.Series(dtype=np.float64), pd.Series(dtype=np.int32)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "tenor": f64, "next_tenor": f64, "d_min": f64, "x_min": f64, "d_atm": f64, "n_cross": i32,
+                             "x_first": f64, "x_last": f64, "flags": i32})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
+
+
+def price_frame(reports: Sequence[PriceReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per (snapshot with quotes > 0, option of the book), ordered by (underlying, date) with the options in the
+    book's order: columns underlying, date, spot, strike, expiry, tau, w, vol, call, put, fwd_var, g, local_vol, flags."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        n, Q = len(keep), len(p.strikes)
+        cols = {"underlying": p.underlying, "date": p.dates[keep].repeat(Q), "spot": np.repeat(_host(r.spot)[keep], Q),
+                "strike": np.tile(p.strikes, n), "expiry": p.expiries[np.tile(np.arange(Q), n)], "tau": p.tau[keep].reshape(-1)}
+        for k in ("w", "vol", "call", "put", "fwd_var", "g", "local_vol"):
+            cols[k] = _host(getattr(p, k))[keep].reshape(-1)
+        cols["flags"] = _host(p.flags)[keep].reshape(-1).astype(np.int32)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "strike": f64, "expiry": pd.Series(dtype="datetime64[ns]"), "tau": f64, "w": f64, "vol": f64, "call": f64,
+                             "put": f64, "fwd_var": f64, "g": f64, "local_vol": f64, "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
