@@ -33,6 +33,7 @@ VOLINDEX_TABLE = "iv_volindex"
 SVI_TABLE = "iv_svi"
 DISTRIBUTION_TABLE = "iv_distribution"
 CALENDAR_TABLE = "iv_calendar"
+SSVI_TABLE = "iv_ssvi"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -388,6 +389,41 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "calendar_pairs": n_cal, "wing_pairs": n_wing, "duration": duration}
 
+    def run_ssvi(self) -> dict:
+        """Arbitrage-free SSVI surfaces: the snapshots of run_surfaces and the slices of run_svi, then one
+        (rho, eta, gamma) per snapshot fitted jointly across its tenors on the device, and one `iv_ssvi` table per underlying
+        (one row per live slice: columns underlying, date, spot, tenor, theta, a, b, rho, m, sigma, rmse_vol, max_vol_err,
+        g_min, flags, and the snapshot's eta, gamma, rmse, sflags).  Returns run_svi's keys plus ssvi_surfaces, raised_rows."""
+        from iv_interpolation_amd import _lib
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, ssvi_frame, ssvi_slices_frame
+        print("\nSSVI: ARBITRAGE-FREE SURFACE PER SNAPSHOT (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the SSVI surfaces"}
+        start = time.time()
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_fit = n_bf = n_surf = n_raised = 0
+        for res, fit in zip(results, builder.svi(results)):
+            sv = _host_flags(fit.flags)[_host_flags(res.quotes) > 0]
+            n_fit += int(((sv & _lib.SV_DEAD) == 0).sum())
+            n_bf += int(((sv & _lib.SV_BUTTERFLY) != 0).sum())
+            rep = builder.ssvi([res], [fit])
+            surf, table = ssvi_frame(rep, [res]), ssvi_slices_frame(rep, [res])
+            table = table.merge(surf[["date", "eta", "gamma", "rmse", "sflags"]], on="date", how="left")
+            self.store.write_table(SSVI_TABLE, res.underlying, table)
+            n_rows += len(table)
+            good = int(((surf["sflags"].to_numpy() & (_lib.SF_SURF_DEAD | _lib.SF_UNORDERED)) == 0).sum())
+            raised = int(surf["raised_rows"].sum())
+            n_surf += good
+            n_raised += raised
+            print(f"  {res.underlying}: {len(surf)} snapshots, {good} surfaces, {len(table)} slices, {raised} raised")
+        duration = time.time() - start
+        print(f"\nSSVI COMPLETE: {duration:.1f}s, underlyings {len(results)}, rows {n_rows:,}, surfaces {n_surf:,}, raised {n_raised:,}")
+        return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
+                "ssvi_surfaces": n_surf, "raised_rows": n_raised, "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -426,7 +462,7 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -475,6 +511,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_distribution()
             elif args.task == "calendar":
                 result = pipeline.run_calendar()
+            elif args.task == "ssvi":
+                result = pipeline.run_ssvi()
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -587,6 +587,79 @@ typedef struct ivs_eval_args {
 int ivs_svi_eval_f64(const ivs_eval_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Arbitrage-free SSVI surface per snapshot, fitted jointly across tenors (rules J1-J8; additive to ABI
+ * 5).  One (rho, eta, gamma) per snapshot and one ATM total variance theta_j per tenor:
+ * w_j(x) = theta_j / 2 (1 + rho phi_j x + sqrt((phi_j x + rho)^2 + 1 - rho^2)), phi_j = eta theta_j^-gamma, fitted to the total
+ * variances w = vol^2 tau at x = ln(k / spot) - rate tau of every valid node of every live row, in least squares of
+ * (w_fit - w) / theta_j.  theta_j is the running maximum of theta0 in tenor order (no calendar arbitrage), gamma stays in [0, 1]
+ * and eta = exp(s) eta_max with s <= 0, eta_max the largest eta with theta phi (1 + |rho|) <= 4 and theta phi^2 (1 + |rho|) <= 4 on
+ * every slice (no butterfly arbitrage).  A fixed number of rounds of a 6 x 6 x 6 grid search over rho in [-1 + 2^-10, 1 - 2^-10],
+ * gamma in [0, 1], s in [ln 2^-10, 0]; deterministic, no data-dependent loop counts.  With the inputs of ivs_svi_slices_f64:
+ *
+ *   vol [B][mT][mK], Kq / kq_stride, Tq / tq_stride, spot [B], rate      as there; the valid strikes need not ascend
+ *   raw [B][mT][5] or theta0 [B][mT]   where theta0 comes from, exactly one non-NULL: theta0 itself, or raw SVI slices (the
+ *                                      `params` of ivs_svi_slices_f64), theta0 = w_j(0) of a slice that is live by the rule of
+ *                                      ivs_svi_distribution_f64, NaN otherwise
+ *   rounds                             rounds of the grid search; 0 = the default 20, 1..32 otherwise.  A round shrinks the
+ *                                      box to 2/5 of its width
+ *   surface [B][4]                     rho, eta, gamma, rmse = sqrt(SSE / n) of the relative residuals
+ *   theta [B][mT]                      theta_j
+ *   params [B][mT][5]                  the slice in raw SVI form: a = theta (1 - rho^2) / 2, b = theta phi / 2, rho,
+ *                                      m = -rho / phi, sigma = sqrt(1 - rho^2) / phi
+ *   fit [B][mT][3]                     rmse_vol and max_vol_err of the fitted vol sqrt(w_fit / tau) against vol over the row's
+ *                                      valid nodes, g_min = the minimum there of Durrleman's g on the raw form; NaN for a live
+ *                                      row without a valid node
+ *   flags [B][mT] (int32)              IVS_SS_*: DEAD (alone, NaN in every value of the row) = spot[b], the tenor or theta0 is
+ *                                      not a finite positive number, or the snapshot is SURF_DEAD or UNORDERED; HOLES = an
+ *                                      invalid node between two valid ones; RAISED = theta_j > theta0_j; BUTTERFLY = g_min < 0
+ *                                      (a guard against rounding, not a regular outcome)
+ *   sflags [B] (int32)                 IVS_SF_*: SURF_DEAD = no live row or fewer than 5 valid nodes on the live rows;
+ *                                      UNORDERED = the live tenors do not ascend strictly (both: NaN in every value of the
+ *                                      snapshot); EDGE_RHO, EDGE_GAMMA, EDGE_ETA_LOW = the final point lies on that border or
+ *                                      within 2^-20 of the domain's width of it; AT_BOUND = s within that band of 0: eta sits
+ *                                      on the butterfly bound
+ *   fitted [B][mT][mK] or NULL         the fitted vol at every node whose strike is a finite positive number; NaN elsewhere.
+ *                                      NULL: not computed, nothing is touched
+ * Every element of every requested output is written, bitwise deterministically (plain stores, no atomics), in ONE launch of
+ * one workgroup per snapshot.  IVS_EINVAL: null args or a null required pointer, both or neither of raw / theta0, a negative
+ * size, a stride that is neither 0 nor the full size; IVS_ERANGE: mT > 64, mK < 1, mT*mK > 3072 (the valid nodes of a snapshot
+ * live in LDS), rounds outside 0..32, B*mT*mK >= 2^31; B == 0 or mT == 0 is a no-op.  No workspace, no allocation, no
+ * synchronisation (capturable).
+ */
+enum {
+    IVS_SS_RAISED     = 1,
+    IVS_SS_HOLES      = 4,
+    IVS_SS_DEAD       = 8,
+    IVS_SS_BUTTERFLY  = 16
+};
+enum {
+    IVS_SF_EDGE_RHO     = 1,
+    IVS_SF_EDGE_GAMMA   = 2,
+    IVS_SF_EDGE_ETA_LOW = 4,
+    IVS_SF_SURF_DEAD    = 8,
+    IVS_SF_AT_BOUND     = 16,
+    IVS_SF_UNORDERED    = 32
+};
+typedef struct ivs_ssvi_args {
+    const double* vol;
+    const double* Kq; int64_t kq_stride;
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* raw;    /* [B][mT][5] or NULL */
+    const double* theta0; /* [B][mT] or NULL */
+    int32_t mK, mT; int64_t B;
+    int32_t rounds;   /* 0 = 20 */
+    double* surface;  /* [B][4]  rho, eta, gamma, rmse */
+    double* theta;    /* [B][mT] */
+    double* params;   /* [B][mT][5]  a, b, rho, m, sigma */
+    double* fit;      /* [B][mT][3]  rmse_vol, max_vol_err, g_min */
+    int32_t* flags;   /* [B][mT] */
+    int32_t* sflags;  /* [B] */
+    double* fitted;   /* [B][mT][mK], may be NULL */
+} ivs_ssvi_args;
+int ivs_ssvi_surface_f64(const ivs_ssvi_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -635,7 +708,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
- * dispatched to (host string); ivs_svi_calendar_f64 and ivs_svi_eval_f64 set it too */
+ * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64 and ivs_ssvi_surface_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

@@ -29,6 +29,10 @@ DS_MAX_PROBS, DS_MAX_LEVELS = 16, 16
 SC_CALENDAR, SC_WING_LEFT, SC_WING_RIGHT, SC_DEAD, SC_LAST, SC_UNORDERED = 1, 2, 4, 8, 16, 32
 SE_SHORT, SE_LONG, SE_NEG_FWD, SE_DEAD, SE_NEG_G, SE_UNORDERED = 1, 2, 4, 8, 16, 32
 ST_MAX_TENORS, SC_MAX_ROWS_PER_WAVE = 64, 32
+# IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
+SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
+SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
+SS_MAX_ROUNDS, SS_MAX_NODES = 32, 3072
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -156,6 +160,14 @@ class EvalArgs(C.Structure):
                 ("w", _p), ("vol", _p), ("call", _p), ("put", _p), ("fwd_var", _p), ("g", _p), ("local_vol", _p), ("flags", _p)]
 
 
+class SsviArgs(C.Structure):
+    """ivs_ssvi_args of include/ivs.h (field for field)."""
+    _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
+                ("spot", _p), ("rate", C.c_double), ("raw", _p), ("theta0", _p),
+                ("mK", _i32), ("mT", _i32), ("B", _i64), ("rounds", _i32),
+                ("surface", _p), ("theta", _p), ("params", _p), ("fit", _p), ("flags", _p), ("sflags", _p), ("fitted", _p)]
+
+
 # every symbol include/ivs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ivs_version": (C.c_int, []),
@@ -192,6 +204,7 @@ SIGNATURES = {
     "ivs_svi_distribution_f64": (C.c_int, [C.POINTER(DistributionArgs), _p, _sz, _p]),
     "ivs_svi_calendar_f64": (C.c_int, [C.POINTER(CalendarArgs), _p, _sz, _p]),
     "ivs_svi_eval_f64": (C.c_int, [C.POINTER(EvalArgs), _p, _sz, _p]),
+    "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),
 }

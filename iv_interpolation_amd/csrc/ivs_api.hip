@@ -19,6 +19,7 @@
 #include "ivs_smile.hpp"
 #include "ivs_snapshot.hpp"
 #include "ivs_svi.hpp"
+#include "ivs_ssvi.hpp"
 #include "ivs_surface_dense.hpp"
 #include "ivs_surface_dense_var2.hpp"
 #include "ivs_surface_pass.hpp"
@@ -645,6 +646,42 @@ int ivs_svi_eval_f64(const ivs_eval_args* a, void* workspace, size_t workspace_b
     hipLaunchKernelGGL(ivs::svi_eval_kernel, dim3((unsigned)grid), dim3(ivs::SE_BLOCK), 0, static_cast<hipStream_t>(stream), p);
     g_last_kernel = "svi_eval_kernel";
     return check_launch("svi_eval_kernel");
+}
+
+int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_ssvi_surface_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if ((a->raw != nullptr) == (a->theta0 != nullptr))
+        return fail(IVS_EINVAL, "%s: exactly one of raw and theta0 must be given", fn);
+    if (a->mT > ivs::SS_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one ballot", fn, a->mT, ivs::SS_MAX_T);
+    if (a->mK < 1) return fail(IVS_ERANGE, "%s: mK=%d < 1", fn, a->mK);
+    if ((int64_t)a->mT * a->mK > ivs::SS_MAX_NODES)
+        return fail(IVS_ERANGE, "%s: mT*mK=%lld > %d nodes of the LDS", fn, (long long)a->mT * a->mK, ivs::SS_MAX_NODES);
+    if (a->rounds < 0 || a->rounds > ivs::SS_MAX_ROUNDS)
+        return fail(IVS_ERANGE, "%s: rounds=%d outside [0,%d]", fn, a->rounds, ivs::SS_MAX_ROUNDS);
+    if (a->B == 0 || a->mT == 0) return IVS_OK;
+    if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->surface || !a->theta || !a->params || !a->fit || !a->flags || !a->sflags)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
+        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+    if (a->B > 0x7fffffffLL / ((int64_t)a->mT * a->mK))
+        return fail(IVS_ERANGE, "%s: %lld x %d x %d nodes exceed one launch", fn, (long long)a->B, a->mT, a->mK);
+    ivs::SsviParams p{};
+    p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot; p.raw = a->raw; p.theta0 = a->theta0;
+    p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate;
+    p.mK = a->mK; p.mT = a->mT;
+    p.rounds = a->rounds == 0 ? ivs::SS_DEFAULT_ROUNDS : a->rounds;
+    p.surface = a->surface; p.theta = a->theta; p.params = a->params; p.fit = a->fit;
+    p.flags = a->flags; p.sflags = a->sflags; p.fitted = a->fitted;
+    const size_t lds = (size_t)a->mT * a->mK * 16;          // one workgroup per snapshot, its valid nodes in LDS
+    hipLaunchKernelGGL(ivs::ssvi_surface_kernel, dim3((unsigned)a->B), dim3(ivs::SS_THREADS), lds,
+                       static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "ssvi_surface_kernel";
+    return check_launch("ssvi_surface_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

@@ -417,6 +417,75 @@ def svi_slices(vol, Kq, Tq, spot, rate: float = 0.0, *, rounds: int = 0, fitted:
     return {k: out[k] for k in want}
 
 
+def ssvi_surface(vol, Kq, Tq, spot, rate: float = 0.0, *, raw=None, theta0=None, rounds: int = 0, fitted: bool = False,
+                 out=None, stream=None):
+    """Arbitrage-free SSVI surface of every snapshot, fitted jointly across its tenors (ivs_ssvi_surface_f64; rules J1-J8 of
+    DESIGN.md section 15).  vol float64 [B,mT,mK] (the `out` of surface_batch); Kq [mK] or [B,mK]; Tq [mT] or [B,mT]; spot [B];
+    all CUDA tensors; mT <= 64, mK >= 1, mT * mK <= 3072 (ValueError outside).  rate: the scalar r of the forward.
+    raw / theta0: where the ATM total variances come from, exactly one of the two (ValueError otherwise): raw float64
+    [B,mT,5] = the `params` of svi_slices, or theta0 float64 [B,mT] itself.
+    rounds: rounds of the 6 x 6 x 6 grid search over (rho, gamma, ln(eta / eta_max)); 0 = the default 20, 1..32 otherwise
+    (ValueError outside).  fitted: True also returns the fitted vol at every strike; False leaves it out (it is neither
+    computed nor written).
+    `out`: optional dict of preallocated outputs (keys surface float64 [B,4], theta float64 [B,mT], params float64 [B,mT,5],
+    fit float64 [B,mT,3], flags int32 [B,mT], sflags int32 [B], fitted float64 [B,mT,mK]).
+    Returns dict(surface, theta, params, fit, flags, sflags, fitted) of device tensors (fitted None when left out); surface =
+    rho, eta, gamma, rmse; params = a, b, rho, m, sigma (the layout of svi_slices); fit = rmse_vol, max_vol_err, g_min; flags
+    are the _lib.SS_* bits, sflags the _lib.SF_* bits."""
+    if not 0 <= int(rounds) <= _lib.SS_MAX_ROUNDS:
+        raise ValueError(f"rounds {rounds!r} is outside [0, {_lib.SS_MAX_ROUNDS}]")
+    if (raw is None) == (theta0 is None):
+        raise ValueError("exactly one of raw and theta0 must be given")
+    torch = require_device()
+    lib = _lib.load()
+    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if vol.dim() != 3:
+        raise ValueError("vol must be [B, mT, mK]")
+    B, mT, mK = vol.shape
+    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
+        raise ValueError("Kq must be [mK] or [B, mK]")
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+    if mT > _lib.ST_MAX_TENORS:
+        raise ValueError(f"mT = {mT}: at most {_lib.ST_MAX_TENORS} tenors per snapshot are supported")
+    if mK < 1 or mT * mK > _lib.SS_MAX_NODES:
+        raise ValueError(f"mT x mK = {mT} x {mK}: between 1 and {_lib.SS_MAX_NODES} nodes per snapshot are supported")
+    if raw is not None:
+        raw = _f64(torch, raw, "raw")
+        if tuple(raw.shape) != (B, mT, 5):
+            raise ValueError("raw must be [B, mT, 5]")
+    else:
+        theta0 = _f64(torch, theta0, "theta0")
+        if tuple(theta0.shape) != (B, mT):
+            raise ValueError("theta0 must be [B, mT]")
+    out = dict(out or {})
+    want = {"surface": ((B, 4), torch.float64, True), "theta": ((B, mT), torch.float64, True),
+            "params": ((B, mT, 5), torch.float64, True), "fit": ((B, mT, 3), torch.float64, True),
+            "flags": ((B, mT), torch.int32, True), "sflags": ((B,), torch.int32, True),
+            "fitted": ((B, mT, mK), torch.float64, bool(fitted))}
+    for k, (shape, dt, on) in want.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    a = _lib.SsviArgs()
+    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
+    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.raw, a.theta0 = _ptr(raw), _ptr(theta0)
+    a.mK, a.mT, a.B, a.rounds = mK, mT, B, int(rounds)
+    a.surface, a.theta, a.params, a.fit = _ptr(out["surface"]), _ptr(out["theta"]), _ptr(out["params"]), _ptr(out["fit"])
+    a.flags, a.sflags, a.fitted = _ptr(out["flags"]), _ptr(out["sflags"]), _ptr(out["fitted"])
+    rc = lib.ivs_ssvi_surface_f64(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, raw, theta0, *out.values())
+    _lib.check(rc, "ivs_ssvi_surface_f64")
+    return {k: out[k] for k in want}
+
+
 DEFAULT_PROBS = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)      # rule P9: the probability cone
 DEFAULT_LEVELS = (0.8, 0.9, 1.0, 1.1, 1.2)                     # ... and the moneyness levels
 

@@ -22,6 +22,9 @@ existing surface path (``engine.surface_batch``):
     pairs = calendar_frame(cal, res)
     marks = b.price(res, book, v)        # vol, call, put, forward variance, local vol of a book of (strike, expiry)
     priced = price_frame(marks, res)
+    s = b.ssvi(res, v)                   # one arbitrage-free SSVI surface per snapshot: DESIGN.md section 15
+    surf, slices = ssvi_frame(s, res), ssvi_slices_frame(s, res)
+    cal2 = b.calendar(res, s)            # an SsviReport goes wherever an SviReport does: distribution, calendar, price
 
 The host does the per-contract bookkeeping (symbol parsing, expiry instants, axes, the cell table) with vectorised
 NumPy / pandas; the per-row work -- minute flooring, last-row-wins, the out-of-the-money choice, expiry masking, quote
@@ -134,6 +137,26 @@ class SviReport:
 
 
 @dataclass
+class SsviReport:
+    """One underlying's SSVI surfaces (rules J1-J8), one per snapshot.  `params` holds every slice in raw SVI form, the layout
+    of SviReport.params: an SsviReport is accepted as `svi_reports` by distribution(), calendar() and price().  The arrays are
+    device tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tenors: np.ndarray               # [mT]
+    moneyness: np.ndarray            # [mK]
+    rate: float
+    rounds: int                      # as asked: 0 = the default 20
+    surface: object                  # [B, 4]: rho, eta, gamma, rmse
+    theta: object                    # [B, mT]
+    params: object                   # [B, mT, 5]: a, b, rho, m, sigma
+    fit: object                      # [B, mT, 3]: rmse_vol, max_vol_err, g_min
+    flags: object                    # [B, mT] int32, IVS_SS_*
+    sflags: object                   # [B] int32, IVS_SF_*
+    fitted: object                   # [B, mT, mK] fitted vols, or None
+
+
+@dataclass
 class DistributionReport:
     """One underlying's risk-neutral quantiles and probabilities (rules P1-P8).  The arrays are device tensors with the HIP
     backend (host arrays with an injected CPU backend)."""
@@ -232,6 +255,12 @@ class HipBackend:
         torch = engine.require_device()
         return engine.svi_slices(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, rounds=rounds,
                                  fitted=fitted, stream=self.stream)
+
+    def ssvi(self, vol, Kq, Tq, spot, rate, raw, theta0, rounds, fitted):
+        from . import engine
+        torch = engine.require_device()
+        return engine.ssvi_surface(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, raw=raw, theta0=theta0,
+                                   rounds=rounds, fitted=fitted, stream=self.stream)
 
     def distribution(self, params, Tq, spot, rate, probs, levels, max_tail):
         from . import engine
@@ -433,6 +462,24 @@ class SnapshotSurfaceBuilder:
             v = be.svi(r.out, r.Kq, r.tenors, r.spot, float(rate), int(rounds), bool(fitted))
             reports.append(SviReport(r.underlying, r.dates, r.tenors, r.moneyness, float(rate), int(rounds), v["params"], v["fit"],
                                      v["flags"], v["fitted"]))
+        return reports
+
+    # ------------------------------------------------------------------ ssvi
+    def ssvi(self, results: Sequence[SnapshotSurfaces], svi_reports=None, rate: float = 0.0, rounds: int = 0,
+             fitted: bool = False) -> List[SsviReport]:
+        """One arbitrage-free SSVI surface per snapshot of `results`, fitted jointly across its tenors (rules J1-J8): one
+        SsviReport per underlying, arrays on the device.  The ATM total variances come from the raw slices of svi_reports (the
+        SviReports of svi(results, rate)); None runs svi(results, rate) first.  rounds: 0 = the default 20, 1..32 otherwise
+        (ValueError outside); fitted=True also keeps the fitted vols [B, mT, mK]."""
+        if int(rounds) != rounds or not 0 <= int(rounds) <= 32:
+            raise ValueError(f"rounds must be 0 (the default) or 1..32, got {rounds!r}")
+        svi_reports = self._slices(results, svi_reports, rate, 0)
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v in zip(results, svi_reports):
+            s = be.ssvi(r.out, r.Kq, r.tenors, r.spot, float(rate), v.params, None, int(rounds), bool(fitted))
+            reports.append(SsviReport(r.underlying, r.dates, r.tenors, r.moneyness, float(rate), int(rounds), s["surface"], s["theta"],
+                                      s["params"], s["fit"], s["flags"], s["sflags"], s["fitted"]))
         return reports
 
     # ------------------------------------------------------------------ distribution
@@ -724,6 +771,53 @@ def svi_frame(reports: Sequence[SviReport], snapshots: Sequence[SnapshotSurfaces
         f64 = pd.Series(dtype=np.float64)
         return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
                              "tenor": f64, "a": f64, "b": f64, "rho": f64, "m": f64, "sigma": f64, "rmse_vol": f64,
+                             "max_vol_err": f64, "g_min": f64, "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
+
+
+def ssvi_frame(reports: Sequence[SsviReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per snapshot with quotes > 0, ordered by (underlying, date): columns underlying, date, spot, rho, eta, gamma,
+    rmse, live_rows, raised_rows, sflags."""
+    parts = []
+    for s, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        su, fl = _host(s.surface)[keep], _host(s.flags)[keep].astype(np.int32)
+        live = (fl & 8) == 0                                                 # IVS_SS_DEAD
+        parts.append(pd.DataFrame({
+            "underlying": s.underlying, "date": s.dates[keep], "spot": _host(r.spot)[keep],
+            "rho": su[:, 0], "eta": su[:, 1], "gamma": su[:, 2], "rmse": su[:, 3],
+            "live_rows": live.sum(axis=1).astype(np.int32), "raised_rows": (live & ((fl & 1) != 0)).sum(axis=1).astype(np.int32),
+            "sflags": _host(s.sflags)[keep].astype(np.int32)}))
+    if not parts:
+        f64, i32 = pd.Series(dtype=np.float64), pd.Series(dtype=np.int32)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "rho": f64, "eta": f64, "gamma": f64, "rmse": f64, "live_rows": i32, "raised_rows": i32, "sflags": i32})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def ssvi_slices_frame(reports: Sequence[SsviReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per (snapshot with quotes > 0, live row), ordered by (underlying, date, tenor): columns underlying, date, spot,
+    tenor, theta, a, b, rho, m, sigma, rmse_vol, max_vol_err, g_min, flags."""
+    parts = []
+    for s, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        fl = _host(s.flags)[keep].astype(np.int32)
+        b, j = np.nonzero((fl & 8) == 0)                                     # IVS_SS_DEAD
+        pr, ft = _host(s.params)[keep], _host(s.fit)[keep]
+        cols = {"underlying": s.underlying, "date": s.dates[keep][b], "spot": _host(r.spot)[keep][b], "tenor": s.tenors[j],
+                "theta": _host(s.theta)[keep][b, j]}
+        for q, name in enumerate(("a", "b", "rho", "m", "sigma")):
+            cols[name] = pr[b, j, q]
+        for q, name in enumerate(("rmse_vol", "max_vol_err", "g_min")):
+            cols[name] = ft[b, j, q]
+        cols["flags"] = fl[b, j]
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "tenor": f64, "theta": f64, "a": f64, "b": f64, "rho": f64, "m": f64, "sigma": f64, "rmse_vol": f64,
                              "max_vol_err": f64, "g_min": f64, "flags": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date", "tenor"], kind="stable").reset_index(drop=True)
