@@ -16,7 +16,8 @@
 //                             previous candle is lane-parallel; the previous-close chain (spread_simulation,
 //                             trend_following) is walked over the valid lanes with v_readlane broadcasts
 // Arithmetic order follows the reference statement by statement (fp contraction off); Python's round(x, n) on
-// floats (correctly rounded decimal, exact ties to even) is emulated exactly with an FMA residual.
+// floats (correctly rounded decimal, exact ties to even) is emulated with an FMA residual below |x| * 10^n = 2^53 and is
+// x itself from there on; tested for n = 4 and 6 (see py_round).
 #pragma once
 #include "ivs_device.hpp"
 
@@ -105,9 +106,14 @@ __device__ __forceinline__ double mt_double(uint32_t w0, uint32_t w1) {
 // ---------------------------------------------------------------- helpers
 // Python's round(x, nd) for a float x (floatobject.c double_round: correctly rounded decimal, exact ties to even),
 // p10 = 10^nd.  x * p10 = p + e exactly (FMA residual); only an exact tie of p can be tipped by e.
+// From |x| * p10 >= 2^53 on Python returns x itself: ulp(x) > |x| * 2^-53 >= 1 / p10 there, so the nearest multiple of
+// 1 / p10 is less than half an ulp away and converts back to x (the product may be inexact or overflow; it is not used).
+// Below 2^53 r is the correctly rounded integer and r / p10 the correctly rounded quotient.  Checked against Python's
+// round for nd = 4 and 6 on the table of tests/bridge_edges_cases.py (ties, near-ties, denormals, both sides of 2^53 / p10,
+// up to 1e305); other digit counts are not used.
 __device__ __forceinline__ double py_round(double x, double p10) {
 #pragma clang fp contract(off)
-    if (!(__builtin_fabs(x) < __builtin_inf())) return x;
+    if (!(__builtin_fabs(x) * p10 < 9007199254740992.0)) return x;      // also NaN, +-inf and an overflowing product
     const double p = x * p10;
     const double e = __builtin_fma(x, p10, -p);
     double r = __builtin_rint(p);
