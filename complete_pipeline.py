@@ -34,13 +34,15 @@ SVI_TABLE = "iv_svi"
 DISTRIBUTION_TABLE = "iv_distribution"
 CALENDAR_TABLE = "iv_calendar"
 SSVI_TABLE = "iv_ssvi"
+IMPLIED_TABLE = "iv_implied"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
 class CompleteOptimizedPipeline:
     def __init__(self, config, data_dir: Optional[str] = None, backend=None, bridge_backend=None, candle_backend=None,
-                 seed: Optional[int] = None, surface_backend=None):
+                 seed: Optional[int] = None, surface_backend=None, implied_backend=None):
         self.config = config
+        self._implied_backend = implied_backend          # None -> implied.HipImpliedBackend
         self._surface_backend = surface_backend          # None -> snapshots.HipBackend
         self.store = FrameStore(data_dir or config.data_dir)
         self._bridge_backend = bridge_backend            # None -> HipBridgeBackend / HipCandleBackend on first use
@@ -424,6 +426,50 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "ssvi_surfaces": n_surf, "raised_rows": n_raised, "duration": duration}
 
+    def run_implied(self) -> dict:
+        """Vol implied by the stored mark: every row of interpolated_trading_tickers that carries a
+        mark_price goes through the price -> vol solver in price_mode "underlying" (mark_price is quoted in units of the
+        underlying) with the row's own interest_rate, time_to_maturity, strike, callput and underlying_price, all rows of an
+        underlying in one launch, and one `iv_implied` table per underlying is written (columns symbol, date, iv,
+        iv_from_mark, iv_diff, flags).  The result counts the rows per flag."""
+        from iv_interpolation_amd.implied import HipImpliedBackend, count_flags
+        print("\nIMPLIED: VOL IMPLIED BY THE STORED MARK (MI355X engine)")
+        print("-" * 40)
+        groups = {}
+        for sym in self.store.symbols("interpolated_trading_tickers"):
+            df = self.store.read_output(sym)
+            if df is None or df.empty or "mark_price" not in df.columns:
+                continue
+            df = df[pd.to_numeric(df["mark_price"], errors="coerce").notna()]
+            if df.empty:
+                continue
+            side = df["callput"].astype(str).str.lower().str[:1] if "callput" in df.columns else pd.Series("", index=df.index)
+            side = side.where(side.isin(["c", "p"]), "p" if sym.lower().endswith("-p") else "c")     # interpolated rows may lack it
+            cols = {k: pd.to_numeric(df[k], errors="coerce").to_numpy(np.float64)
+                    for k in ("iv", "mark_price", "underlying_price", "strike", "time_to_maturity", "interest_rate")}
+            groups.setdefault(sym.split("-")[0], []).append(pd.DataFrame(
+                {"symbol": sym, "date": df["date"].to_numpy(), **cols, "is_put": (side == "p").to_numpy(np.uint8)}))
+        if not groups:
+            return {"success": False, "error": "No interpolated rows with a mark_price found"}
+        start = time.time()
+        be = self._implied_backend or HipImpliedBackend()
+        flags = []
+        for underlying in sorted(groups):
+            g = pd.concat(groups[underlying], ignore_index=True)
+            q = be.implied_vol(*[g[k].to_numpy(np.float64) for k in ("mark_price", "underlying_price", "strike", "time_to_maturity", "interest_rate")],
+                               g["is_put"].to_numpy(np.uint8), price_mode=1)
+            vol, fl = np.asarray(q["vol"], np.float64), np.asarray(q["flags"], np.int32)
+            table = pd.DataFrame({"symbol": g["symbol"], "date": g["date"], "iv": g["iv"], "iv_from_mark": vol,
+                                  "iv_diff": vol - g["iv"].to_numpy(), "flags": fl})
+            self.store.write_table(IMPLIED_TABLE, underlying, table)
+            flags.append(fl)
+            print(f"  {underlying}: {len(table)} rows, {int(np.isfinite(vol).sum())} with a vol")
+        counts = count_flags(np.concatenate(flags))
+        duration = time.time() - start
+        n_rows = sum(len(f) for f in flags)
+        print(f"\nIMPLIED COMPLETE: {duration:.1f}s, underlyings {len(groups)}, rows {n_rows:,}, solved {counts['solved_rows']:,}")
+        return {"success": n_rows > 0, "underlyings": len(groups), "rows": n_rows, **counts, "duration": duration}
+
     def run_complete_pipeline(self, test_mode: bool = False, symbol_limit: int = None) -> dict:
         """Reference :740-831: Task 1 -> bridge -> Task 2 over the same symbol list, stopping at the first failed stage."""
         symbols = self.store.symbols()
@@ -460,9 +506,9 @@ def _host_flags(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
 
 
-def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None):
+def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "all"], default="all")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -473,7 +519,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
     try:
         config = get_config()
         pipeline = CompleteOptimizedPipeline(config, data_dir=args.data_dir, backend=backend, bridge_backend=bridge_backend,
-                                             candle_backend=candle_backend, seed=seed, surface_backend=surface_backend)
+                                             candle_backend=candle_backend, seed=seed, surface_backend=surface_backend,
+                                             implied_backend=implied_backend)
         if args.synthetic:
             for i in range(args.synthetic):
                 sym = f"btc-20mar23-{20000 + 500 * i}-c"
@@ -495,6 +542,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 symbols = pipeline.store.symbols()[:3 if args.test else args.symbols]
             if args.task == "interpolation":
                 result = pipeline.run_task1_interpolation(symbols)
+            elif args.task == "implied":
+                result = pipeline.run_implied()
             elif args.task == "bridge":
                 result = pipeline.run_data_bridge(symbols)
             elif args.task == "surfaces":

@@ -669,6 +669,45 @@ int ivs_bs_greeks_f64(const double* S, const double* K, const double* T, const d
                       double* theta, double* vega, double* rho, void* stream);
 
 /*
+ * Black-Scholes prices and their inverse, price -> implied volatility (rules V1-V8): elementwise over n
+ * options, one launch per call.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.  With D = exp(-r T),
+ * KD = K D and x = log(S/K) + r T:
+ *
+ * ivs_bs_price_f64: call = S Phi(d1) - KD Phi(d2), put = KD Phi(-d2) - S Phi(-d1), d1 = x/s + s/2, d2 = d1 - s,
+ * s = sigma sqrt(T).  An option is live iff S, K, T, r, sigma are finite and S, K, T, sigma > 0; otherwise NaN and IVS_IV_DEAD.
+ *   price [n]                          required
+ *   vega [n]                           S phi(d1) sqrt(T), per unit of vol (NOT per 1 % like ivs_bs_greeks_f64); may be NULL
+ *   flags [n] (int32)                  IVS_IV_DEAD or 0; may be NULL.  An output left out is neither computed nor written.
+ *
+ * ivs_bs_implied_vol_f64: the vol at which the formula above gives `price`.  price_mode 0: P = price; 1: P = price S (a
+ * price quoted in units of the underlying, as the chains' mark_price is).  An option is live iff price, S, K, T, r are
+ * finite, S, K, T > 0 and price >= 0; otherwise NaN and IVS_IV_DEAD alone.  The bounds are compared in price space:
+ * P >= S (call) or KD (put) is IVS_IV_ABOVE (NaN); P below the intrinsic value max(S - KD, 0) / max(KD - S, 0) is
+ * IVS_IV_BELOW (NaN), P equal to it IVS_IV_BELOW with vol 0.  An in-the-money option (call with x > 0, put with x < 0) carries
+ * IVS_IV_ITM and is solved through parity on its time value P - intrinsic.  The total vol s solves
+ * exp(-h/2) Phi(-h/s + s/2) - exp(h/2) Phi(-h/s - s/2) = tv / sqrt(S KD), h = |x|, by 64 halvings of log2 s on [-40, 6] in
+ * every lane; a solution outside [2^-40, 2^6] gives that border and IVS_IV_EDGE.  vol = s / sqrt(T).
+ *   vol [n], flags [n] (int32)         both required
+ *
+ * IVS_EINVAL: a null required pointer, n < 0, a price_mode that is not 0 or 1; IVS_ERANGE: n >= 2^31; n == 0 is a no-op.  A
+ * refused call launches nothing.  No workspace, no allocation, no synchronisation (capturable).  The results do not depend on
+ * n, on the option's position or on the launch geometry, bit for bit.
+ */
+enum {
+    IVS_IV_ITM        = 1,
+    IVS_IV_BELOW      = 2,
+    IVS_IV_ABOVE      = 4,
+    IVS_IV_DEAD       = 8,
+    IVS_IV_EDGE       = 16
+};
+int ivs_bs_price_f64(const double* S, const double* K, const double* T, const double* r, const double* sigma,
+                     const uint8_t* is_put, int32_t default_is_put, int64_t n,
+                     double* price, double* vega /* may be NULL */, int32_t* flags /* may be NULL */, void* stream);
+int ivs_bs_implied_vol_f64(const double* price, const double* S, const double* K, const double* T, const double* r,
+                           const uint8_t* is_put, int32_t default_is_put, int32_t price_mode, int64_t n,
+                           double* vol, int32_t* flags, void* stream);
+
+/*
  * N-minute candle aggregation (reference src/candle_reconstruction/core.py:68-88) for S symbols (CSR series_off [S+1],
  * rows sorted by timestamp within a symbol).  For every input row i: if it is the first row of its
  * floor(ts / freq_ns) bucket, out_*[i] holds the bucket's candle (open = first non-NaN, high = max, low = min,
@@ -708,7 +747,8 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
- * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64 and ivs_ssvi_surface_f64 set it too */
+ * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64 and
+ * ivs_bs_implied_vol_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

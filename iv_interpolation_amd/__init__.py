@@ -9,6 +9,7 @@ include/ivs.h; torch-ROCm is used only for device buffers, streams and torch.dis
 from ._lib import (CUBIC, CUBICSPLINE, LINEAR, METHOD_CODES, SLINEAR, ST_OK, ST_TOO_FEW_KNOTS,  # noqa: F401
                    EngineError, EngineUnavailable)
 from .core import IVInterpolator  # noqa: F401
+from .implied import ImpliedVolatility  # noqa: F401
 
-__all__ = ["IVInterpolator", "EngineUnavailable", "EngineError", "METHOD_CODES",
+__all__ = ["IVInterpolator", "ImpliedVolatility", "EngineUnavailable", "EngineError", "METHOD_CODES",
            "LINEAR", "CUBIC", "CUBICSPLINE", "SLINEAR", "ST_OK", "ST_TOO_FEW_KNOTS"]

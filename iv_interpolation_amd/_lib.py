@@ -33,6 +33,8 @@ ST_MAX_TENORS, SC_MAX_ROWS_PER_WAVE = 64, 32
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
 SS_MAX_ROUNDS, SS_MAX_NODES = 32, 3072
+# IVS_IV_*: per-option flags of the implied-vol solver (the pricer knows DEAD only)
+IV_ITM, IV_BELOW, IV_ABOVE, IV_DEAD, IV_EDGE = 1, 2, 4, 8, 16
 FLAG_FORCE_GENERIC = 1
 FLAG_ONE_PASS = 2          # IVS_FLAG_ONE_PASS: skip the row-pass kernels (testing / A-B timing)
 
@@ -187,6 +189,8 @@ SIGNATURES = {
     "ivs_frame_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "ivs_frame_columns_f64": (C.c_int, [C.POINTER(FrameArgs), _p, _sz, _p]),
     "ivs_bs_greeks_f64": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p, _p, _p]),
+    "ivs_bs_price_f64": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p]),
+    "ivs_bs_implied_vol_f64": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _p, _p]),
     "ivs_candle_aggregate_f64": (C.c_int, [_p] * 7 + [_i64, _i64, _i64] + [_p] * 8),
     "ivs_bridge_workspace_bytes": (C.c_size_t, [_i64]),
     "ivs_mt19937_words_u32": (C.c_int, [C.c_uint32, _p, _i64, _p]),

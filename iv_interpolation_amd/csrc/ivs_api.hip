@@ -15,6 +15,7 @@
 #include "ivs_svi_surface.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
+#include "ivs_implied.hpp"
 #include "ivs_moments.hpp"
 #include "ivs_smile.hpp"
 #include "ivs_snapshot.hpp"
@@ -777,6 +778,39 @@ int ivs_bs_greeks_f64(const double* S, const double* K, const double* T, const d
     ivs::GreeksParams p{S, K, T, r, sigma, is_put, default_is_put, n, delta, gamma, theta, vega, rho};
     hipLaunchKernelGGL(ivs::greeks_kernel, dim3((unsigned)ivs::capped_blocks(n, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return check_launch("greeks_kernel");
+}
+
+int ivs_bs_price_f64(const double* S, const double* K, const double* T, const double* r, const double* sigma,
+                     const uint8_t* is_put, int32_t default_is_put, int64_t n, double* price, double* vega, int32_t* flags,
+                     void* stream) {
+    const char* fn = "ivs_bs_price_f64";
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (n < 0) return fail(IVS_EINVAL, "%s: negative size n=%lld", fn, (long long)n);
+    if (n > 0x7fffffffLL) return fail(IVS_ERANGE, "%s: n=%lld options exceed one launch", fn, (long long)n);
+    if (n == 0) return IVS_OK;
+    if (!S || !K || !T || !r || !sigma || !price) return fail(IVS_EINVAL, "%s: null pointer", fn);
+    ivs::BsPriceParams p{S, K, T, r, sigma, is_put, default_is_put, n, price, vega, flags};
+    hipLaunchKernelGGL(ivs::bs_price_kernel, dim3((unsigned)ivs::capped_blocks(n, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "bs_price_kernel";
+    return check_launch("bs_price_kernel");
+}
+
+int ivs_bs_implied_vol_f64(const double* price, const double* S, const double* K, const double* T, const double* r,
+                           const uint8_t* is_put, int32_t default_is_put, int32_t price_mode, int64_t n, double* vol,
+                           int32_t* flags, void* stream) {
+    const char* fn = "ivs_bs_implied_vol_f64";
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (n < 0) return fail(IVS_EINVAL, "%s: negative size n=%lld", fn, (long long)n);
+    if (price_mode != 0 && price_mode != 1) return fail(IVS_EINVAL, "%s: price_mode=%d is neither 0 nor 1", fn, price_mode);
+    if (n > 0x7fffffffLL) return fail(IVS_ERANGE, "%s: n=%lld options exceed one launch", fn, (long long)n);
+    if (n == 0) return IVS_OK;
+    if (!price || !S || !K || !T || !r || !vol || !flags) return fail(IVS_EINVAL, "%s: null pointer", fn);
+    ivs::ImpliedParams p{price, S, K, T, r, is_put, default_is_put, price_mode, n, vol, flags};
+    hipLaunchKernelGGL(ivs::bs_implied_vol_kernel, dim3((unsigned)ivs::capped_blocks(n, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "bs_implied_vol_kernel";
+    return check_launch("bs_implied_vol_kernel");
 }
 
 size_t ivs_surface_workspace_bytes(int64_t B, int32_t ragged) { return ivs::surface_ws_bytes(B, ragged != 0); }

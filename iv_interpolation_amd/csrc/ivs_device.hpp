@@ -15,6 +15,10 @@ constexpr int WAVE = 64;
 
 __device__ __forceinline__ double qnan() { return __builtin_nan(""); }
 
+// the standard normal's distribution function and density, shared by every kernel that prices or differentiates
+__device__ __forceinline__ double norm_cdf(double x) { return 0.5 * erfc(-x * 0.70710678118654752440); }
+__device__ __forceinline__ double norm_pdf(double x) { return exp(-x * x * 0.5) * 0.39894228040143267794; }
+
 // Largest j in [0, n) with x(j) <= xq, or -1.  NaN xq -> -1.
 template <class XA>
 __device__ __forceinline__ int find_interval(const XA& x, int n, double xq) {

@@ -13,9 +13,6 @@ struct GreeksParams {
     double* delta; double* gamma; double* theta; double* vega; double* rho;
 };
 
-__device__ __forceinline__ double norm_cdf(double x) { return 0.5 * erfc(-x * 0.70710678118654752440); }
-__device__ __forceinline__ double norm_pdf(double x) { return exp(-x * x * 0.5) * 0.39894228040143267794; }
-
 // one option: the reference's formulas statement by statement (greeks.py:21-35)
 __device__ __forceinline__ void bs_greeks_one(double S, double K, double T, double r, double sg, bool put, double& delta,
                                               double& gamma, double& theta, double& vega, double& rho) {

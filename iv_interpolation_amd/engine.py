@@ -879,6 +879,77 @@ def bs_greeks(S, K, T, r, sigma, is_put=None, default_is_put: bool = False, stre
     return dict(zip(("delta", "gamma", "theta", "vega", "rho"), outs))
 
 
+def _option_inputs(torch, tensors, names, is_put):
+    """The shared input checks of bs_price and bs_implied_vol: CUDA float64 tensors of one size, is_put uint8 / bool or None."""
+    ins = [_f64(torch, t, n) for t, n in zip(tensors, names)]
+    n = ins[0].numel()
+    if any(t.numel() != n for t in ins):
+        raise ValueError(f"{', '.join(names)} must have the same number of elements")
+    if is_put is not None:
+        if not is_put.is_cuda or is_put.numel() != n:
+            raise ValueError("is_put must be a CUDA tensor with one entry per option")
+        is_put = is_put.to(torch.uint8).contiguous()
+    return ins, n, is_put
+
+
+def _option_outputs(torch, out, want, like):
+    """`want`: key -> (dtype, on).  Outputs of like's shape, taken from `out` (checked) or allocated; None where off."""
+    out = dict(out or {})
+    res = {}
+    for k, (dt, on) in want.items():
+        t = out.get(k)
+        if not on:
+            res[k] = None
+        elif t is None:
+            res[k] = torch.empty(like.shape, dtype=dt, device=like.device)
+        elif t.numel() != like.numel() or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor with one entry per option")
+        else:
+            res[k] = t
+    return res
+
+
+def bs_price(S, K, T, r, sigma, is_put=None, default_is_put: bool = False, want_vega: bool = False, out=None, stream=None,
+             want_flags: bool = True):
+    """Black-Scholes prices on the device (ivs_bs_price_f64; rules V1, V8 of DESIGN.md section 16).  All inputs CUDA float64
+    tensors of one size (is_put: uint8 / bool or None -> default_is_put for every option).  vega is per unit of vol, not per
+    1 % like bs_greeks'.  `out`: optional dict of preallocated outputs (price, vega float64, flags int32).  An output that is
+    not wanted is neither computed nor written (None in the result).
+    Returns dict(price, vega, flags) of tensors with S's shape; flags is _lib.IV_DEAD or 0."""
+    torch = require_device()
+    lib = _lib.load()
+    ins, n, is_put = _option_inputs(torch, (S, K, T, r, sigma), ("S", "K", "T", "r", "sigma"), is_put)
+    res = _option_outputs(torch, out, {"price": (torch.float64, True), "vega": (torch.float64, bool(want_vega)),
+                                       "flags": (torch.int32, bool(want_flags))}, ins[0])
+    rc = lib.ivs_bs_price_f64(*[_ptr(t) for t in ins], _ptr(is_put), int(bool(default_is_put)), n,
+                              _ptr(res["price"]), _ptr(res["vega"]), _ptr(res["flags"]), _stream(torch, stream))
+    _hold_for_stream(torch, stream, *ins, is_put, *res.values())
+    _lib.check(rc, "ivs_bs_price_f64")
+    return res
+
+
+PRICE_MODES = {"quote": 0, "underlying": 1}
+
+
+def bs_implied_vol(price, S, K, T, r, is_put=None, default_is_put: bool = False, price_mode: int = 0, out=None, stream=None):
+    """Price -> Black-Scholes implied volatility on the device (ivs_bs_implied_vol_f64; rules V1-V7 of DESIGN.md section 16).
+    All inputs CUDA float64 tensors of one size (is_put: uint8 / bool or None -> default_is_put for every option).
+    price_mode: 0 = `price` is in the units of S and K, 1 = `price` is quoted in units of the underlying (P = price S, as the
+    chains' mark_price is); ValueError otherwise.  `out`: optional dict of preallocated outputs (vol float64, flags int32).
+    Returns dict(vol, flags) of tensors with price's shape; the flags are the _lib.IV_* bits."""
+    if price_mode not in (0, 1):
+        raise ValueError(f"price_mode {price_mode!r} is neither 0 (quote) nor 1 (units of the underlying)")
+    torch = require_device()
+    lib = _lib.load()
+    ins, n, is_put = _option_inputs(torch, (price, S, K, T, r), ("price", "S", "K", "T", "r"), is_put)
+    res = _option_outputs(torch, out, {"vol": (torch.float64, True), "flags": (torch.int32, True)}, ins[0])
+    rc = lib.ivs_bs_implied_vol_f64(*[_ptr(t) for t in ins], _ptr(is_put), int(bool(default_is_put)), int(price_mode), n,
+                                    _ptr(res["vol"]), _ptr(res["flags"]), _stream(torch, stream))
+    _hold_for_stream(torch, stream, *ins, is_put, *res.values())
+    _lib.check(rc, "ivs_bs_implied_vol_f64")
+    return res
+
+
 def candle_aggregate(ts_ns, o, h, l, c, v, series_off, freq_minutes: int, stream=None):
     """Sparse N-minute aggregation on the device (see ivs_candle_aggregate_f64).  ts_ns int64, OHLCV float64, series_off
     int64 [S+1]; all CUDA tensors.  Returns (out_ts, open, high, low, close, volume, count) of length n."""
