@@ -35,6 +35,8 @@ DISTRIBUTION_TABLE = "iv_distribution"
 CALENDAR_TABLE = "iv_calendar"
 SSVI_TABLE = "iv_ssvi"
 IMPLIED_TABLE = "iv_implied"
+RISK_TABLE = "iv_risk"
+SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
 
@@ -328,6 +330,65 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "duration": duration}
 
+    def run_risk(self, book_file: Optional[str] = None) -> dict:
+        """Book risk: the snapshots of run_surfaces and the slices of run_svi, then the smile-aware
+        Greeks of a book of options, its net Greeks and its scenario P&L grid per snapshot on the device.  The book is every
+        listed contract of the chain (rule S1) with quantity +1, or the CSV `book_file` with the columns symbol, quantity
+        (symbols of the chain; one not listed, one listed twice or a quantity that is not a finite number is an error; an
+        underlying without an option of the book gets no tables).  One `iv_risk` table (columns underlying, date, spot, price,
+        delta_ss, delta_sm, gamma_ss, gamma_sm, vega, theta, gross, n_dead) and one `iv_scenarios` table (columns underlying,
+        date, spot, spot_shock, vol_shock, dynamic, pnl, flags) per underlying."""
+        from iv_interpolation_amd import _lib
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, listed_book, risk_frame, scenario_frame
+        print("\nRISK: SMILE-AWARE GREEKS AND SCENARIO P&L OF A BOOK (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the book risk"}
+        start = time.time()
+        book = listed_book(frames)
+        if book_file:
+            held = pd.read_csv(book_file)
+            for c in ("symbol", "quantity"):
+                if c not in held.columns:
+                    return {"success": False, "error": f"{book_file}: no column {c!r}"}
+            held = held.assign(symbol=held["symbol"].astype(str), quantity=pd.to_numeric(held["quantity"], errors="coerce"))
+            unknown = sorted(set(held["symbol"]) - set(book["symbol"]))
+            if unknown:
+                return {"success": False, "error": f"{book_file}: not listed in the chain: {unknown[:4]}"}
+            twice = sorted(set(held["symbol"][held["symbol"].duplicated()]))
+            if twice:
+                return {"success": False, "error": f"{book_file}: listed more than once: {twice[:4]}"}
+            bad = held["symbol"][~np.isfinite(held["quantity"].to_numpy(np.float64))].tolist()
+            if bad:
+                return {"success": False, "error": f"{book_file}: the quantity is not a finite number: {bad[:4]}"}
+            book = book.drop(columns="quantity").merge(held[["symbol", "quantity"]], on="symbol", how="inner")
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_fit = n_bf = n_risk = n_scen = n_dead = 0
+        for res, fit in zip(results, builder.svi(results)):
+            sv = _host_flags(fit.flags)[_host_flags(res.quotes) > 0]
+            n_rows += sv.size
+            n_fit += int(((sv & _lib.SV_DEAD) == 0).sum())
+            n_bf += int(((sv & _lib.SV_BUTTERFLY) != 0).sum())
+            held = book[book["underlying"] == res.underlying].reset_index(drop=True)
+            if held.empty:                                   # no position in this underlying: no tables for it
+                print(f"  {res.underlying}: no option of the book, skipped")
+                continue
+            rep = builder.risk([res], held, [fit])
+            table, scen = risk_frame(rep, [res]), scenario_frame(rep, [res])
+            self.store.write_table(RISK_TABLE, res.underlying, table)
+            self.store.write_table(SCENARIO_TABLE, res.underlying, scen)
+            dead = int(table["n_dead"].sum())
+            n_risk += len(table)
+            n_scen += len(scen)
+            n_dead += dead
+            print(f"  {res.underlying}: {len(held)} options, {len(table)} snapshots, {len(scen)} scenario rows, {dead} dead option marks")
+        duration = time.time() - start
+        print(f"\nRISK COMPLETE: {duration:.1f}s, underlyings {len(results)}, snapshots {n_risk:,}, scenario rows {n_scen:,}, dead {n_dead:,}")
+        return {"success": n_risk > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
+                "risk_rows": n_risk, "scenario_rows": n_scen, "dead_options": n_dead, "duration": duration}
+
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
         quantiles, level probabilities and tails of every tenor row on the device, and one `iv_distribution` table per
@@ -508,7 +569,8 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "all"], default="all")
+    parser.add_argument("--book", metavar="FILE", help="--task risk: a CSV of symbol, quantity (default: every listed contract, +1 each)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -562,6 +624,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_calendar()
             elif args.task == "ssvi":
                 result = pipeline.run_ssvi()
+            elif args.task == "risk":
+                result = pipeline.run_risk(args.book)
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

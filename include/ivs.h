@@ -660,6 +660,87 @@ typedef struct ivs_ssvi_args {
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Book risk off the raw SVI slices: smile-aware Greeks per option, net Greeks and a scenario P&L grid per snapshot (DESIGN.md
+ * section 17, rules G0-G6, B1-B5; additive to ABI 5).  Both calls read params / Tq / tq_stride / spot / rate / u / tau /
+ * q_stride / strike_mode exactly as ivs_svi_eval_f64 does and place an option on the surface by its rules: K, x, D, W, W', W'',
+ * V and the flags IVS_SE_SHORT, LONG, DEAD, UNORDERED.  is_put [Q] (uint8, 1 = put, one list for all snapshots) or NULL = all
+ * calls.  With theta = sqrt(W), theta' = W'/(2 theta), theta'' = W''/(2 theta) - W'^2/(4 theta^3), d1 = -x/theta + theta/2,
+ * d2 = d1 - theta, d1x = -1/theta + (x/theta^2 + 1/2) theta', d2x = d1x - theta', S = spot:
+ *
+ * ivs_svi_greeks_f64, each value [B][Q] and each may be NULL (then neither computed nor written):
+ *   price                              call S Phi(d1) - K D Phi(d2), put K D Phi(-d2) - S Phi(-d1)
+ *   delta_ss, gamma_ss                 sticky strike: Phi(d1) (put: -Phi(-d1)) and phi(d1) / (S theta)
+ *   delta_sm, gamma_sm                 sticky moneyness (the curve in x is fixed): delta_ss - phi(d1) theta' and
+ *                                      phi(d1) (-d2x - d1 d1x theta' + theta'' - theta') / S
+ *   vega                               S phi(d1) sqrt(tau), per unit of vol for a parallel shift
+ *   theta                              per year, -d price / d tau at fixed K and S: -S [+-rate (K D / S) Phi(+-d2) +
+ *                                      phi(d1) (V - rate W') / (2 theta)], + for a call, - for a put
+ *   flags [B][Q] (int32)               IVS_SE_SHORT, LONG, NEG_FWD (V < 0; theta is still the formula's value), DEAD,
+ *                                      UNORDERED; required.  A dead option has NaN values.
+ *
+ * ivs_svi_book_f64: besides qty [Q] (one list for all snapshots; an option whose quantity is not finite is dead too), nA spot
+ * shocks a and nV vol shocks v (host arrays).  Cell (i, k): S' = S (1 + a_i), x' = log(K / S') - rate tau, vol
+ * sqrt(W(x) / tau) + v_k (sticky strike) or sqrt(W(x') / tau) + v_k (sticky moneyness, the option's bracket and weight
+ * unchanged), theta' = vol sqrt(tau), the price formula above at (S', x', theta').  The base price P of the P&L is that of the
+ * cell with both shocks zero.
+ *   net [B][8]                         sum over the live options of qty x (price, delta_ss, delta_sm, gamma_ss, gamma_sm,
+ *                                      vega, theta) and, in slot 7, of |qty| x price
+ *   n_dead [B] (int32)                 the dead options; they contribute nothing
+ *   pnl_ss, pnl_sm [B][nA][nV]         sum of qty (P' - P) over the live options; either may be NULL.  Exactly +0.0 where
+ *                                      a_i == 0 and v_k == 0
+ *   cell_flags [B][nA][nV] (int32)     IVS_SB_NEG_VOL_SS / _SM: a live option has a shocked vol <= 0 in the cell under that
+ *                                      dynamic; the cell's value is then NaN.  Required.  The bit of a dynamic whose pnl output is
+ *                                      NULL is not formed (it is skipped with that dynamic's arithmetic) and stays 0.
+ * An UNORDERED snapshot or one without a live slice has NaN in every net and pnl entry, n_dead = Q and cell flags 0.
+ * Every sum is formed without atomics in an order that depends on Q alone (an xor butterfly over the 64 lanes of a wavefront,
+ * four wavefronts as (s0 + s1) + (s2 + s3), passes of 256 options in turn): the bits do not depend on B, on cells_per_wg or on
+ * the run.  cells_per_wg: how many cells one workgroup takes; 0 lets the call choose, 1..256 forces it.
+ *
+ * IVS_EINVAL: null args or a null required pointer, a negative size, a stride that is neither 0 nor the full size, a
+ * strike_mode that is not 0 or 1; IVS_ERANGE: mT > 64, nA or nV > 64, nA nV > 1024, cells_per_wg outside 0..256, a spot shock
+ * that is not finite or <= -1, a vol shock that is not finite, B*mT, B*Q or B*nA*nV >= 2^31.  B == 0, mT == 0 or Q == 0 is a
+ * no-op for both (nothing is written: the caller defines what an empty book is worth; engine.svi_book fills zeros); the
+ * limits above and the shocks are checked before that, so a zero-size call with a bad shock is refused all the same.  With
+ * nA nV == 0 net and n_dead are still written.  A refused call
+ * launches nothing.  No workspace, no allocation, no synchronisation (capturable); ONE launch each.
+ */
+enum {
+    IVS_SB_NEG_VOL_SS = 1,
+    IVS_SB_NEG_VOL_SM = 2
+};
+typedef struct ivs_greeks_args {
+    const double* params; /* [B][mT][5]  a, b, rho, m, sigma */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* u; const double* tau; int64_t q_stride; /* [Q] (stride 0) or [B][Q] (stride Q) */
+    const uint8_t* is_put; /* [Q] or NULL */
+    int32_t strike_mode; /* 0: K = spot u; 1: K = u */
+    int32_t mT; int64_t Q; int64_t B;
+    double* price; double* delta_ss; double* delta_sm; double* gamma_ss; double* gamma_sm; double* vega; double* theta; /* [B][Q], each may be NULL */
+    int32_t* flags;   /* [B][Q] */
+} ivs_greeks_args;
+int ivs_svi_greeks_f64(const ivs_greeks_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+typedef struct ivs_book_args {
+    const double* params; /* [B][mT][5] */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* u; const double* tau; int64_t q_stride;
+    const uint8_t* is_put; /* [Q] or NULL */
+    const double* qty;     /* [Q] */
+    int32_t strike_mode;
+    int32_t mT; int64_t Q; int64_t B;
+    const double* spot_shocks; /* host */ int32_t nA;
+    const double* vol_shocks;  /* host */ int32_t nV;
+    double* net;       /* [B][8] */
+    int32_t* n_dead;   /* [B] */
+    double* pnl_ss; double* pnl_sm; /* [B][nA][nV], each may be NULL */
+    int32_t* cell_flags;            /* [B][nA][nV] */
+    int32_t cells_per_wg; /* 0 = chosen by the call; 1..256 = tuning / testing override, same bits */
+} ivs_book_args;
+int ivs_svi_book_f64(const ivs_book_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -747,8 +828,8 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
- * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64 and
- * ivs_bs_implied_vol_f64 set it too */
+ * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64,
+ * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64 and ivs_svi_book_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

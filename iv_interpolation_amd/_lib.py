@@ -29,6 +29,9 @@ DS_MAX_PROBS, DS_MAX_LEVELS = 16, 16
 SC_CALENDAR, SC_WING_LEFT, SC_WING_RIGHT, SC_DEAD, SC_LAST, SC_UNORDERED = 1, 2, 4, 8, 16, 32
 SE_SHORT, SE_LONG, SE_NEG_FWD, SE_DEAD, SE_NEG_G, SE_UNORDERED = 1, 2, 4, 8, 16, 32
 ST_MAX_TENORS, SC_MAX_ROWS_PER_WAVE = 64, 32
+# IVS_SB_*: per-cell flags of the scenario grid of a book, one bit per dynamic
+SB_NEG_VOL_SS, SB_NEG_VOL_SM = 1, 2
+RK_MAX_SHOCKS, RK_MAX_GRID = 64, 1024
 # IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
@@ -162,6 +165,23 @@ class EvalArgs(C.Structure):
                 ("w", _p), ("vol", _p), ("call", _p), ("put", _p), ("fwd_var", _p), ("g", _p), ("local_vol", _p), ("flags", _p)]
 
 
+class GreeksArgs(C.Structure):
+    """ivs_greeks_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("u", _p), ("tau", _p), ("q_stride", _i64), ("is_put", _p), ("strike_mode", _i32), ("mT", _i32), ("Q", _i64), ("B", _i64),
+                ("price", _p), ("delta_ss", _p), ("delta_sm", _p), ("gamma_ss", _p), ("gamma_sm", _p), ("vega", _p), ("theta", _p),
+                ("flags", _p)]
+
+
+class BookArgs(C.Structure):
+    """ivs_book_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("u", _p), ("tau", _p), ("q_stride", _i64), ("is_put", _p), ("qty", _p), ("strike_mode", _i32), ("mT", _i32),
+                ("Q", _i64), ("B", _i64),
+                ("spot_shocks", C.POINTER(C.c_double)), ("nA", _i32), ("vol_shocks", C.POINTER(C.c_double)), ("nV", _i32),
+                ("net", _p), ("n_dead", _p), ("pnl_ss", _p), ("pnl_sm", _p), ("cell_flags", _p), ("cells_per_wg", _i32)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -208,6 +228,8 @@ SIGNATURES = {
     "ivs_svi_distribution_f64": (C.c_int, [C.POINTER(DistributionArgs), _p, _sz, _p]),
     "ivs_svi_calendar_f64": (C.c_int, [C.POINTER(CalendarArgs), _p, _sz, _p]),
     "ivs_svi_eval_f64": (C.c_int, [C.POINTER(EvalArgs), _p, _sz, _p]),
+    "ivs_svi_greeks_f64": (C.c_int, [C.POINTER(GreeksArgs), _p, _sz, _p]),
+    "ivs_svi_book_f64": (C.c_int, [C.POINTER(BookArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

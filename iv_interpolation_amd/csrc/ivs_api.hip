@@ -13,6 +13,7 @@
 #include "ivs_candles.hpp"
 #include "ivs_distribution.hpp"
 #include "ivs_svi_surface.hpp"
+#include "ivs_risk.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
 #include "ivs_implied.hpp"
@@ -647,6 +648,98 @@ int ivs_svi_eval_f64(const ivs_eval_args* a, void* workspace, size_t workspace_b
     hipLaunchKernelGGL(ivs::svi_eval_kernel, dim3((unsigned)grid), dim3(ivs::SE_BLOCK), 0, static_cast<hipStream_t>(stream), p);
     g_last_kernel = "svi_eval_kernel";
     return check_launch("svi_eval_kernel");
+}
+
+int ivs_svi_greeks_f64(const ivs_greeks_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_svi_greeks_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->Q < 0 || a->tq_stride < 0 || a->q_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->strike_mode != 0 && a->strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, a->strike_mode);
+    if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, a->mT, ivs::ST_MAX_T);
+    if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;
+    if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->flags) return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if ((a->tq_stride != 0 && a->tq_stride != a->mT) || (a->q_stride != 0 && a->q_stride != a->Q))
+        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (a->B > 0x7fffffffLL / a->Q)
+        return fail(IVS_ERANGE, "%s: %lld x %lld options exceed one launch", fn, (long long)a->B, (long long)a->Q);
+    ivs::RiskParams p{};
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put;
+    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
+    p.mT = a->mT; p.strike_mode = a->strike_mode; p.Q = a->Q;
+    p.nqb = (int32_t)((a->Q + ivs::RK_BLOCK - 1) / ivs::RK_BLOCK);
+    p.out[0] = a->price; p.out[1] = a->delta_ss; p.out[2] = a->delta_sm; p.out[3] = a->gamma_ss; p.out[4] = a->gamma_sm;
+    p.out[5] = a->vega; p.out[6] = a->theta;
+    p.flags = a->flags;
+    const int64_t grid = a->B * p.nqb;                      // <= B * Q < 2^31
+    hipLaunchKernelGGL(ivs::svi_greeks_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "svi_greeks_kernel";
+    return check_launch("svi_greeks_kernel");
+}
+
+int ivs_svi_book_f64(const ivs_book_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_svi_book_f64";
+    (void)workspace; (void)workspace_bytes;                 // no device scratch
+    g_err[0] = 0;
+    g_last_kernel = "";
+    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (a->B < 0 || a->mT < 0 || a->Q < 0 || a->nA < 0 || a->nV < 0 || a->tq_stride < 0 || a->q_stride < 0)
+        return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->strike_mode != 0 && a->strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, a->strike_mode);
+    if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, a->mT, ivs::ST_MAX_T);
+    if (a->nA > ivs::RK_MAX_SHOCKS || a->nV > ivs::RK_MAX_SHOCKS)
+        return fail(IVS_ERANGE, "%s: nA=%d or nV=%d > %d shocks per axis", fn, a->nA, a->nV, ivs::RK_MAX_SHOCKS);
+    if (a->nA * a->nV > ivs::RK_MAX_GRID) return fail(IVS_ERANGE, "%s: nA*nV=%d > %d cells", fn, a->nA * a->nV, ivs::RK_MAX_GRID);
+    if (a->cells_per_wg < 0 || a->cells_per_wg > ivs::RK_MAX_CELLS)
+        return fail(IVS_ERANGE, "%s: cells_per_wg=%d outside [0,%d]", fn, a->cells_per_wg, ivs::RK_MAX_CELLS);
+    const int ncell = a->nA * a->nV;
+    if (ncell > 0 && (!a->spot_shocks || !a->vol_shocks)) return fail(IVS_EINVAL, "%s: null shocks", fn);
+    for (int i = 0; ncell > 0 && i < a->nA; ++i)
+        if (!(a->spot_shocks[i] > -1.0 && a->spot_shocks[i] < __builtin_inf()))
+            return fail(IVS_ERANGE, "%s: spot shock %d (%g) is not a finite number above -1", fn, i, a->spot_shocks[i]);
+    for (int k = 0; ncell > 0 && k < a->nV; ++k)
+        if (!(a->vol_shocks[k] > -__builtin_inf() && a->vol_shocks[k] < __builtin_inf()))
+            return fail(IVS_ERANGE, "%s: vol shock %d (%g) is not finite", fn, k, a->vol_shocks[k]);
+    if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;
+    if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->qty || !a->net || !a->n_dead) return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (ncell > 0 && !a->cell_flags) return fail(IVS_EINVAL, "%s: null pointer (cell_flags)", fn);
+    if ((a->tq_stride != 0 && a->tq_stride != a->mT) || (a->q_stride != 0 && a->q_stride != a->Q))
+        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
+    if (a->B > 0x7fffffffLL / a->mT)
+        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (a->B > 0x7fffffffLL / a->Q)
+        return fail(IVS_ERANGE, "%s: %lld x %lld options exceed one launch", fn, (long long)a->B, (long long)a->Q);
+    if (ncell > 0 && a->B > 0x7fffffffLL / ncell)
+        return fail(IVS_ERANGE, "%s: %lld x %d cells exceed one launch", fn, (long long)a->B, ncell);
+    ivs::BookParams p{};
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put; p.qty = a->qty;
+    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
+    p.mT = a->mT; p.strike_mode = a->strike_mode; p.nA = a->nA; p.nV = a->nV; p.Q = a->Q;
+    for (int i = 0; ncell > 0 && i < a->nA; ++i) p.a[i] = a->spot_shocks[i];
+    for (int k = 0; ncell > 0 && k < a->nV; ++k) p.v[k] = a->vol_shocks[k];
+    p.net = a->net; p.n_dead = a->n_dead; p.pnl_ss = a->pnl_ss; p.pnl_sm = a->pnl_sm; p.cell_flags = a->cell_flags;
+    // cells per workgroup: a whole grid of up to 256 cells while the snapshots alone give every CU two workgroups, shorter runs
+    // below that.  The sums of a cell do not depend on the split.
+    int cpb = 0, nchunk = 1;
+    if (ncell > 0) {
+        int dev, cus;
+        current_device(dev, cus);
+        int64_t need = (2 * (int64_t)cus + a->B - 1) / a->B;
+        const int least = (ncell + ivs::RK_MAX_CELLS - 1) / ivs::RK_MAX_CELLS;
+        need = need < least ? least : (need > ncell ? ncell : need);
+        cpb = (int)((ncell + need - 1) / need);
+        if (a->cells_per_wg > 0) cpb = a->cells_per_wg;     // tuning / testing override
+        nchunk = (ncell + cpb - 1) / cpb;
+    }
+    p.cpb = cpb; p.nchunk = nchunk;
+    const int64_t grid = a->B * nchunk;                     // <= B * max(ncell, 1) < 2^31
+    hipLaunchKernelGGL(ivs::svi_book_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
+    g_last_kernel = "svi_book_kernel";
+    return check_launch("svi_book_kernel");
 }
 
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void* workspace, size_t workspace_bytes, void* stream) {

@@ -658,6 +658,155 @@ def svi_eval(params, Tq, spot, rate, u, tau, *, strike_mode: int = 0, want=EVAL_
     return {k: out[k] for k in shapes}
 
 
+GREEK_OUTPUTS = ("price", "delta_ss", "delta_sm", "gamma_ss", "gamma_sm", "vega", "theta")
+BOOK_OUTPUTS = ("pnl_ss", "pnl_sm")
+NET_COLUMNS = GREEK_OUTPUTS + ("gross",)                       # the eight slots of a book's `net`
+DEFAULT_SPOT_SHOCKS = (-0.20, -0.15, -0.10, -0.05, 0.0, 0.05, 0.10, 0.15, 0.20)
+DEFAULT_VOL_SHOCKS = (-0.10, -0.05, 0.0, 0.05, 0.10)
+
+
+def _option_queries(torch, B, u, tau, is_put, qty=None):
+    """The shared checks of the options of svi_greeks / svi_book: u, tau [Q] or [B,Q] of one shape, is_put uint8 / bool [Q] or
+    None, qty float64 [Q]."""
+    u = _f64(torch, u, "u"); tau = _f64(torch, tau, "tau")
+    if u.dim() not in (1, 2) or u.shape != tau.shape or (u.dim() == 2 and u.shape[0] != B):
+        raise ValueError("u and tau must both be [Q] or both [B, Q]")
+    Q = u.shape[-1]
+    if is_put is not None:
+        if not is_put.is_cuda or is_put.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("is_put must be a CUDA uint8 or bool tensor")
+        if tuple(is_put.shape) != (Q,):
+            raise ValueError("is_put must be [Q]: one side per option, shared by all snapshots")
+        is_put = is_put.to(torch.uint8).contiguous()
+    if qty is not None:
+        qty = _f64(torch, qty, "qty")
+        if tuple(qty.shape) != (Q,):
+            raise ValueError("qty must be [Q]: one quantity per option, shared by all snapshots")
+    return u, tau, is_put, qty, Q
+
+
+def _outputs(torch, out, shapes, device):
+    out = dict(out or {})
+    for k, (shape, dt, on) in shapes.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    return out
+
+
+def svi_greeks(params, Tq, spot, rate, u, tau, *, is_put=None, strike_mode: int = 0, want=GREEK_OUTPUTS, out=None, stream=None):
+    """Smile-aware Greeks of options on the surface of the raw SVI slices (ivs_svi_greeks_f64; rules G0-G6 of DESIGN.md section
+    17).  params, Tq, spot, rate, u, tau, strike_mode as in svi_eval; is_put uint8 / bool [Q] (one side per option, shared by
+    all snapshots) or None = all calls.
+    want: which of GREEK_OUTPUTS to compute; one left out is neither computed nor written (None in the result).
+    `out`: optional dict of preallocated outputs (float64 [B,Q] per value, flags int32 [B,Q]).
+    With mT == 0 the C call writes nothing and the wrapper fills NaN and DEAD itself.
+    Returns dict(price, delta_ss, delta_sm, gamma_ss, gamma_sm, vega, theta, flags) of device tensors; the flags are the
+    _lib.SE_* bits SHORT, LONG, NEG_FWD, DEAD, UNORDERED."""
+    if strike_mode not in (0, 1):
+        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    want = tuple(want)
+    if any(k not in GREEK_OUTPUTS for k in want):
+        raise ValueError(f"want must name outputs among {GREEK_OUTPUTS}, got {want!r}")
+    torch = require_device()
+    lib = _lib.load()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    u, tau, is_put, _, Q = _option_queries(torch, B, u, tau, is_put)
+    shapes = {k: ((B, Q), torch.float64, k in want) for k in GREEK_OUTPUTS}
+    shapes["flags"] = ((B, Q), torch.int32, True)
+    out = _outputs(torch, out, shapes, params.device)
+    a = _lib.GreeksArgs()
+    a.params, a.Tq, a.tq_stride, a.spot, a.rate = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.u, a.tau, a.q_stride, a.strike_mode = _ptr(u), _ptr(tau), (0 if u.dim() == 1 else Q), int(strike_mode)
+    a.is_put = _ptr(is_put)
+    a.mT, a.Q, a.B = mT, Q, B
+    for k in GREEK_OUTPUTS:
+        setattr(a, k, _ptr(out[k]))
+    a.flags = _ptr(out["flags"])
+    rc = lib.ivs_svi_greeks_f64(a, None, 0, _stream(torch, stream))
+    if rc == 0 and mT == 0:                                  # the C call is a no-op; without a slice every option is dead (E1)
+        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+            for k in want:
+                out[k].fill_(float("nan"))
+            out["flags"].fill_(_lib.SE_DEAD)
+    _hold_for_stream(torch, stream, params, Tq, spot, u, tau, is_put, *out.values())
+    _lib.check(rc, "ivs_svi_greeks_f64")
+    return {k: out[k] for k in shapes}
+
+
+def book_shocks(spot_shocks, vol_shocks):
+    """The host-side checks of a scenario grid: at most 64 shocks per axis and 1024 cells, every spot
+    shock finite and > -1, every vol shock finite; ValueError otherwise.  Returns (spot_shocks, vol_shocks) as lists."""
+    import math
+    a, v = [float(x) for x in spot_shocks], [float(x) for x in vol_shocks]
+    if len(a) > _lib.RK_MAX_SHOCKS or len(v) > _lib.RK_MAX_SHOCKS or len(a) * len(v) > _lib.RK_MAX_GRID:
+        raise ValueError(f"a {len(a)} x {len(v)} grid: at most {_lib.RK_MAX_SHOCKS} shocks per axis and {_lib.RK_MAX_GRID} cells are supported")
+    if any(not (math.isfinite(x) and x > -1.0) for x in a):
+        raise ValueError(f"spot shocks must be finite and > -1, got {a!r}")
+    if any(not math.isfinite(x) for x in v):
+        raise ValueError(f"vol shocks must be finite, got {v!r}")
+    return a, v
+
+
+def svi_book(params, Tq, spot, rate, u, tau, qty, spot_shocks=DEFAULT_SPOT_SHOCKS, vol_shocks=DEFAULT_VOL_SHOCKS, *, is_put=None,
+             strike_mode: int = 0, want=BOOK_OUTPUTS, out=None, stream=None, cells_per_wg: int = 0):
+    """Net Greeks and the scenario P&L grid of a book of options per snapshot (ivs_svi_book_f64; rules B1-B5 of DESIGN.md
+    section 17).  Inputs as in svi_greeks, besides qty float64 [Q] (one quantity per option, shared by all snapshots; an option
+    whose quantity is not finite is dead) and the two lists of shocks (book_shocks has their limits).
+    want: which of pnl_ss (sticky strike) and pnl_sm (sticky moneyness) to compute.
+    `out`: optional dict of preallocated outputs (net float64 [B,8], n_dead int32 [B], pnl_ss / pnl_sm float64 [B,nA,nV],
+    cell_flags int32 [B,nA,nV]).
+    cells_per_wg: 0 lets the call choose how many cells a workgroup takes; 1..256 forces it (tuning / testing; the results are
+    the same bit for bit).
+    The C call writes nothing when mT == 0 or Q == 0; the wrapper then fills the result itself: without a slice every snapshot is
+    degenerate (NaN, n_dead = Q, cell flags 0), and a book without options has 0 in every sum, count and flag.
+    Returns dict(net, n_dead, pnl_ss, pnl_sm, cell_flags) of device tensors; net's columns are NET_COLUMNS, the cell flags the
+    _lib.SB_* bits."""
+    import ctypes
+    if strike_mode not in (0, 1):
+        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    want = tuple(want)
+    if any(k not in BOOK_OUTPUTS for k in want):
+        raise ValueError(f"want must name outputs among {BOOK_OUTPUTS}, got {want!r}")
+    sa, sv = book_shocks(spot_shocks, vol_shocks)
+    torch = require_device()
+    lib = _lib.load()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
+    nA, nV = len(sa), len(sv)
+    shapes = {"net": ((B, 8), torch.float64, True), "n_dead": ((B,), torch.int32, True),
+              "pnl_ss": ((B, nA, nV), torch.float64, "pnl_ss" in want), "pnl_sm": ((B, nA, nV), torch.float64, "pnl_sm" in want),
+              "cell_flags": ((B, nA, nV), torch.int32, True)}
+    out = _outputs(torch, out, shapes, params.device)
+    abuf, vbuf = (ctypes.c_double * max(nA, 1))(*sa), (ctypes.c_double * max(nV, 1))(*sv)
+    a = _lib.BookArgs()
+    a.params, a.Tq, a.tq_stride, a.spot, a.rate = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.u, a.tau, a.q_stride, a.strike_mode = _ptr(u), _ptr(tau), (0 if u.dim() == 1 else Q), int(strike_mode)
+    a.is_put, a.qty = _ptr(is_put), _ptr(qty)
+    a.mT, a.Q, a.B = mT, Q, B
+    a.spot_shocks, a.nA = ctypes.cast(abuf, ctypes.POINTER(ctypes.c_double)), nA
+    a.vol_shocks, a.nV = ctypes.cast(vbuf, ctypes.POINTER(ctypes.c_double)), nV
+    a.net, a.n_dead, a.cell_flags = _ptr(out["net"]), _ptr(out["n_dead"]), _ptr(out["cell_flags"])
+    a.pnl_ss, a.pnl_sm = _ptr(out["pnl_ss"]), _ptr(out["pnl_sm"])
+    a.cells_per_wg = int(cells_per_wg)
+    rc = lib.ivs_svi_book_f64(a, None, 0, _stream(torch, stream))
+    if rc == 0 and B > 0 and (mT == 0 or Q == 0):            # the C call is a no-op: the result is defined here
+        empty = float("nan") if mT == 0 else 0.0             # B1: no live slice -> NaN and n_dead = Q; a book without options is worth 0
+        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+            out["net"].fill_(empty)
+            out["n_dead"].fill_(Q if mT == 0 else 0)
+            out["cell_flags"].zero_()
+            for k in want:
+                out[k].fill_(empty)
+    _hold_for_stream(torch, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
+    _lib.check(rc, "ivs_svi_book_f64")
+    return {k: out[k] for k in shapes}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -212,6 +212,28 @@ class PriceReport:
     flags: object                    # [B, Q] int32, IVS_SE_*
 
 
+@dataclass
+class RiskReport:
+    """One underlying's book of options with its risk at every snapshot (rules G0-G6, B1-B5).  The value arrays are device
+    tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    strikes: np.ndarray              # [Q]
+    expiries: pd.DatetimeIndex       # [Q]
+    is_put: np.ndarray               # [Q] bool
+    quantity: np.ndarray             # [Q]
+    tau: np.ndarray                  # [B, Q] years from the snapshot to the expiry (<= 0: expired, DEAD)
+    rate: float
+    spot_shocks: np.ndarray          # [nA]
+    vol_shocks: np.ndarray           # [nV]
+    greeks: dict                     # price, delta_ss, delta_sm, gamma_ss, gamma_sm, vega, theta [B, Q]; flags [B, Q] int32, IVS_SE_*
+    net: object                      # [B, 8] sums of quantity x the seven figures, then of |quantity| x price
+    n_dead: object                   # [B] int32
+    pnl_ss: object                   # [B, nA, nV] sticky strike
+    pnl_sm: object                   # [B, nA, nV] sticky moneyness
+    cell_flags: object               # [B, nA, nV] int32, IVS_SB_*
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -278,6 +300,21 @@ class HipBackend:
         torch = engine.require_device()
         d = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()  # noqa: E731
         return engine.svi_eval(params, d(Tq), spot, rate, d(u), d(tau), strike_mode=strike_mode, stream=self.stream)
+
+    def greeks(self, params, Tq, spot, rate, u, tau, is_put, strike_mode):
+        from . import engine
+        torch = engine.require_device()
+        d = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()  # noqa: E731
+        side = torch.from_numpy(np.ascontiguousarray(is_put, np.uint8)).cuda()
+        return engine.svi_greeks(params, d(Tq), spot, rate, d(u), d(tau), is_put=side, strike_mode=strike_mode, stream=self.stream)
+
+    def book(self, params, Tq, spot, rate, u, tau, qty, spot_shocks, vol_shocks, is_put, strike_mode):
+        from . import engine
+        torch = engine.require_device()
+        d = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()  # noqa: E731
+        side = torch.from_numpy(np.ascontiguousarray(is_put, np.uint8)).cuda()
+        return engine.svi_book(params, d(Tq), spot, rate, d(u), d(tau), d(qty), spot_shocks, vol_shocks, is_put=side,
+                               strike_mode=strike_mode, stream=self.stream)
 
 
 def _host(a):
@@ -554,6 +591,47 @@ class SnapshotSurfaceBuilder:
             q = be.evaluate(v.params, r.tenors, r.spot, float(rate), u, tau, 1)
             reports.append(PriceReport(r.underlying, r.dates, strikes, expiry, tau, float(rate), q["w"], q["vol"], q["call"], q["put"],
                                        q["fwd_var"], q["g"], q["local_vol"], q["flags"]))
+        return reports
+
+    # ------------------------------------------------------------------ risk
+    def risk(self, results: Sequence[SnapshotSurfaces], book: pd.DataFrame, svi_reports=None, rate: float = 0.0,
+             spot_shocks=None, vol_shocks=None, rounds: int = 0) -> List["RiskReport"]:
+        """The risk of a book of options at every surface of `results` (rules G0-G6, B1-B5): one RiskReport per underlying
+        with the smile-aware Greeks of every option, the book's net Greeks and its scenario P&L grid under both dynamics.
+        book: price()'s frame (strike, expiry) plus callput (a string that starts with c or p, any case) and quantity
+        (signed; an option whose quantity is not a finite number is dead).  spot_shocks: relative moves of the spot, None =
+        -20 % ... +20 % in steps of 5 %; vol_shocks: absolute moves of the vol, None = -0.10, -0.05, 0, +0.05, +0.10.
+        svi_reports as for calendar()."""
+        from .engine import DEFAULT_SPOT_SHOCKS, DEFAULT_VOL_SHOCKS, book_shocks
+        for c in ("strike", "expiry", "callput", "quantity"):
+            if c not in book.columns:
+                raise KeyError(c)
+        sa, sv = book_shocks(DEFAULT_SPOT_SHOCKS if spot_shocks is None else spot_shocks,
+                             DEFAULT_VOL_SHOCKS if vol_shocks is None else vol_shocks)
+        side = book["callput"].astype(str).str.lower().str[:1]
+        if not side.isin(["c", "p"]).all():
+            raise ValueError("callput must start with c or p")
+        is_put = (side == "p").to_numpy(bool)
+        svi_reports = self._slices(results, svi_reports, rate, rounds)
+        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
+        qty = pd.to_numeric(book["quantity"], errors="coerce").to_numpy(np.float64)
+        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v in zip(results, svi_reports):
+            e = expiry
+            if e.tz is None and r.dates.tz is not None:
+                e = e.tz_localize(r.dates.tz)
+            elif e.tz is not None and r.dates.tz is None:
+                e = e.tz_convert("UTC").tz_localize(None)
+            e_ns, d_ns = e.as_unit("ns").asi8, r.dates.as_unit("ns").asi8
+            tau = (e_ns[None, :] - d_ns[:, None]).astype(np.float64) / float(YEAR_NS)
+            tau[:, np.asarray(e.isna())] = np.nan
+            u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
+            g = be.greeks(v.params, r.tenors, r.spot, float(rate), u, tau, is_put, 1)
+            k = be.book(v.params, r.tenors, r.spot, float(rate), u, tau, qty, sa, sv, is_put, 1)
+            reports.append(RiskReport(r.underlying, r.dates, strikes, expiry, is_put, qty, tau, float(rate), np.asarray(sa), np.asarray(sv),
+                                      dict(g), k["net"], k["n_dead"], k["pnl_ss"], k["pnl_sm"], k["cell_flags"]))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -913,5 +991,98 @@ def price_frame(reports: Sequence[PriceReport], snapshots: Sequence[SnapshotSurf
         return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
                              "strike": f64, "expiry": pd.Series(dtype="datetime64[ns]"), "tau": f64, "w": f64, "vol": f64, "call": f64,
                              "put": f64, "fwd_var": f64, "g": f64, "local_vol": f64, "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def listed_book(data, quantity: float = 1.0) -> pd.DataFrame:
+    """Every listed contract of `data` (a long frame or a list of per-contract frames) as a book: one row per distinct symbol
+    that rule S1 accepts, with underlying, strike, callput and expiry (= date + time_to_maturity x YEAR) of its first row in
+    date order, and `quantity` each.  Columns symbol, underlying, strike, expiry, callput, quantity, in symbol order."""
+    df = SnapshotSurfaceBuilder._long(data)
+    df = df.assign(date=pd.to_datetime(df["date"])).dropna(subset=["symbol", "date"])
+    first = df.sort_values(["symbol", "date"], kind="stable").groupby("symbol", sort=True).head(1)
+    sym = first["symbol"].astype(str)
+    side = first["callput"].astype(str).str[:1].str.lower()
+    strike = pd.to_numeric(first["strike"], errors="coerce")
+    ttm = pd.to_numeric(first["time_to_maturity"], errors="coerce")
+    good = sym.str.fullmatch(_SYMBOL.pattern, flags=re.IGNORECASE) & side.isin(["c", "p"]) & strike.notna() & np.isfinite(ttm)
+    first, sym, side, strike, ttm = first[good], sym[good], side[good], strike[good], ttm[good]
+    expiry = pd.DatetimeIndex(first["date"]) + pd.to_timedelta(np.rint(ttm.to_numpy(np.float64) * float(YEAR_NS)).astype(np.int64), unit="ns")
+    return pd.DataFrame({"symbol": sym.to_numpy(), "underlying": sym.str.lower().str.split("-").str[0].to_numpy(),
+                         "strike": strike.to_numpy(np.float64), "expiry": expiry, "callput": side.to_numpy(),
+                         "quantity": float(quantity)}).reset_index(drop=True)
+
+
+GREEK_COLUMNS = ("price", "delta_ss", "delta_sm", "gamma_ss", "gamma_sm", "vega", "theta")
+
+
+def risk_frame(reports: Sequence[RiskReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per snapshot with quotes > 0, ordered by (underlying, date): columns underlying, date, spot, the book's net
+    price, delta_ss, delta_sm, gamma_ss, gamma_sm, vega, theta, its gross value and n_dead."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        net = _host(p.net)[keep]
+        cols = {"underlying": p.underlying, "date": p.dates[keep], "spot": _host(r.spot)[keep]}
+        for n, k in enumerate(GREEK_COLUMNS + ("gross",)):
+            cols[k] = net[:, n]
+        cols["n_dead"] = _host(p.n_dead)[keep].astype(np.int32)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             **{k: f64 for k in GREEK_COLUMNS + ("gross",)}, "n_dead": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def scenario_frame(reports: Sequence[RiskReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per (snapshot with quotes > 0, cell, dynamic), ordered by (underlying, date) with the cells in the grid's order
+    (spot shocks outermost) and sticky strike before sticky moneyness: columns underlying, date, spot, spot_shock, vol_shock,
+    dynamic ('ss' / 'sm'), pnl, flags (the cell's IVS_SB_* bit of that dynamic, as 0 / 1)."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        nA, nV, n = len(p.spot_shocks), len(p.vol_shocks), len(keep)
+        cf = _host(p.cell_flags)[keep].astype(np.int32)
+        pnl = np.stack([_host(p.pnl_ss)[keep], _host(p.pnl_sm)[keep]], axis=-1)            # [n, nA, nV, 2]
+        fl = np.stack([cf & 1, (cf >> 1) & 1], axis=-1)
+        per = nA * nV * 2
+        parts.append(pd.DataFrame({
+            "underlying": p.underlying, "date": p.dates[keep].repeat(per), "spot": np.repeat(_host(r.spot)[keep], per),
+            "spot_shock": np.tile(np.repeat(p.spot_shocks, nV * 2), n), "vol_shock": np.tile(np.repeat(p.vol_shocks, 2), n * nA),
+            "dynamic": np.tile(np.array(["ss", "sm"], dtype=object), n * nA * nV), "pnl": pnl.reshape(-1),
+            "flags": fl.reshape(-1).astype(np.int32)}))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "spot_shock": f64, "vol_shock": f64, "dynamic": pd.Series(dtype=object), "pnl": f64,
+                             "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def greeks_frame(reports: Sequence[RiskReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per (snapshot with quotes > 0, option of the book), ordered by (underlying, date) with the options in the
+    book's order: columns underlying, date, spot, strike, expiry, callput, quantity, tau, price, delta_ss, delta_sm, gamma_ss,
+    gamma_sm, vega, theta, flags."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        n, Q = len(keep), len(p.strikes)
+        cols = {"underlying": p.underlying, "date": p.dates[keep].repeat(Q), "spot": np.repeat(_host(r.spot)[keep], Q),
+                "strike": np.tile(p.strikes, n), "expiry": p.expiries[np.tile(np.arange(Q), n)],
+                "callput": np.tile(np.where(p.is_put, "p", "c").astype(object), n), "quantity": np.tile(p.quantity, n),
+                "tau": p.tau[keep].reshape(-1)}
+        for k in GREEK_COLUMNS:
+            cols[k] = _host(p.greeks[k])[keep].reshape(-1)
+        cols["flags"] = _host(p.greeks["flags"])[keep].reshape(-1).astype(np.int32)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "spot": f64,
+                             "strike": f64, "expiry": pd.Series(dtype="datetime64[ns]"), "callput": pd.Series(dtype=object),
+                             "quantity": f64, "tau": f64, **{k: f64 for k in GREEK_COLUMNS}, "flags": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
