@@ -461,7 +461,13 @@ __device__ unsigned long long* d_pass_ends = nullptr;
 
 // NT16 (VAR only): the batch has the full 16 maturities (BASELINE config 5): the run-time maturity count -- masked rows, the
 // third tap of the last system row, the select chain for the hold row -- compiles away (~60 VALU instructions per surface).
-template <int METHOD, int NKB, bool VAR, bool TSH = true, bool NT16 = false>
+// KQS: one query-strike grid for the whole batch (kq_stride == 0) as a compile-time property: xq is loaded once ahead of
+// the surface loop and the per-surface reload with its branch does not exist.  With the run-time form the compiler has to
+// treat xq as "maybe in flight" and drains the memory queue -- the next surface's prefetch included -- in front of the
+// strike search and at the loop top.  Instantiated where it measured a gain: the fixed 64 x 16 kernels of
+// every method but the step rules (nearest / zero / from_derivatives lost 0.9 % with it) and the NT16 kernels of
+// linear / slinear (+3.3 % on config 5; cubic did not move there, pchip lost 2.6 %).
+template <int METHOD, int NKB, bool VAR, bool TSH = true, bool NT16 = false, bool KQS = false>
 // Wavefronts per SIMD: 3 (168 VGPRs); the run-time-maturity-count instantiations of pchip / akima need ~200 (the per-lane
 // maturity solve of the local rules) and run at 2 without scratch -- at 3 they spilled 14-36 registers and lost 3-30 %.
 // Their NT16 forms fit 3: pchip 161 VGPRs (48 B of scratch at 65..128 strikes), akima 164 / 166 with the rolling maturity slopes.
@@ -484,6 +490,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
     static_assert(LERP || LOCAL || QUADK || METHOD == IVS_CUBIC || METHOD == IVS_CUBICSPLINE, "methods of the dense kernels");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
+    if (!VAR) __builtin_assume(lane < 64);           // one wavefront: lets `ir < n` and the index clamps fold when n = KCAP
     const int mT = p.mT, mK = p.mK;
     double* Yp = reinterpret_cast<double*>(smem);
     double* Sp = Yp + G::PLANE;
@@ -512,7 +519,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
     // spare slots that are read but never staged must hold finite numbers (they meet zero coefficients)
     for (int i = lane; i < (LERP ? 1 : 2) * G::PLANE; i += 64) Yp[i] = 0.0;
 
-    const bool kq_shared = p.kq_stride == 0;
+    const bool kq_shared = KQS || p.kq_stride == 0;
     const bool act = lane < mK;
     double xq = (kq_shared && act) ? p.Kq[lane] : nanv;
 
@@ -523,7 +530,9 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
     else wq.init(p.queue + list.qslot * 8 * QUEUE_STRIDE, 8, list.items ? (int64_t)*list.count : p.B, PASS_CHUNK, lane);
     auto at = [&](int64_t i, int& n, int64_t& koff) -> int64_t {
         if (VAR && list.items) { const VarItem v = list.items[i]; n = v.n; koff = v.koff; return v.b; }
-        n = p.nK; koff = i * p.k_stride; return i;
+        // the fixed kernel knows its shape (launched with nK == KCAP only).  akima keeps the run-time count: with the constant
+        // the compiler contracts other multiply-add pairs of its secant extension and the outputs move in the last bit
+        n = (VAR || METHOD == IVS_AKIMA) ? p.nK : KCAP; koff = i * p.k_stride; return i;
     };
 
     // ---- prefetch registers: pass ps of a surface lands in slot ps % PFP, requested PFP passes ahead of its staging
@@ -560,6 +569,9 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
     int64_t koff = 0, koff_next = 0, b = 0, b_next = 0;
     int64_t it = wq.take();
     int64_t it_next = it >= 0 ? wq.take() : -1;
+    // pinned here, the wait for xq is the one the first claim pays anyway -- not one in front of the strike search, which
+    // would also wait for the next surface's prefetch
+    if (KQS) asm volatile("" : "+v"(xq));
     if (it >= 0) {
         b = at(it, n, koff);
 #pragma unroll
@@ -582,7 +594,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
         const bool more = it_next >= 0;
         if (more) b_next = at(it_next, n_next, koff_next);
         const WorkQueue::Pending pend = wq.begin(more);       // the surface after next may open a new chunk: claim it now
-        if (!kq_shared) xq = act ? p.Kq[b * p.kq_stride + lane] : nanv;      // issued ahead of the next prefetch (vmcnt is in order)
+        if (!KQS && !kq_shared) xq = act ? p.Kq[b * p.kq_stride + lane] : nanv;      // issued ahead of the next prefetch (vmcnt is in order)
         if (!TSH) {
             __syncthreads();                                   // the previous surface is done with the planes and with TT / W
             dense_t_phase<METHOD, true, NTR>(p.T + b * p.t_stride, p.Tq + b * p.tq_stride, mT, lane, LERP ? Yp : Yp + 600, TTl, Wl, tt, nT, Yp);
@@ -794,8 +806,14 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
             }
         }
         // run-time-shape batches with the full 16 maturities take the NT16 instantiation
+        // ... and where it pays (see KQS) the kernel knows at compile time that the batch shares its query strikes
         with_bool(VAR && nt16, [&](auto n) {
-            hipLaunchKernelGGL((surface_pass_kernel<M, NKB, VAR, true, VAR && decltype(n)::value>), dim3((unsigned)grid), dim3(64), lds, cx.st, p, list);
+            constexpr bool N16 = VAR && decltype(n)::value;
+            constexpr bool KQS_OK = VAR ? N16 && (M == IVS_LINEAR || M == IVS_SLINEAR) : !d_is_step(M);
+            with_bool(KQS_OK && p.kq_stride == 0, [&](auto k) {
+                constexpr bool KQS = KQS_OK && decltype(k)::value;
+                hipLaunchKernelGGL((surface_pass_kernel<M, NKB, VAR, true, N16, KQS>), dim3((unsigned)grid), dim3(64), lds, cx.st, p, list);
+            });
         });
     };
     bool ok = true;
