@@ -669,7 +669,12 @@ __device__ __forceinline__ void dense_t_phase(const double* Tb, const double* Tq
 // NTR: run-time maturity count nT_rt (see dense_t_phase): masked system rows, three-tap last row, hold row = nT_rt - 1.
 // SM: TT and W point at the TqShared tables in global memory; every read of them is a scalar load (uniform index),
 // the next row's weights are requested while the current row is combined and stored.
-template <int METHOD, bool WLDS, bool RANGED = false, bool NTR = false, bool SM = false, class StampFn>
+// RW (SM && !RANGED only): the row walk's bookkeeping.  0: two running 64-bit pointers (weight stream, output row) and a
+// per-row 64-bit address add.  1: ONE 32-bit byte offset per stream -- the weights through the scalar base + offset form of
+// the load, the row store through its scalar-base form with the lane's running 32-bit offset.  2: as 1, and the row's
+// weights are loaded at the use (no request one row ahead, hence no "next -> current" register moves per row).
+// The arithmetic and its order are the same in every form.
+template <int METHOD, bool WLDS, bool RANGED = false, bool NTR = false, bool SM = false, int RW = 0, class StampFn>
 __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const TqTables& tt, const double* TT,
                                                     const double* W, double* outb, int q0, int lane, bool act, int mT,
                                                     int mK, StampFn&& stamp, int row_lo = 0, int row_hi = 0,
@@ -694,12 +699,24 @@ __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const
     int tq = 0;
     double* rp = outb + q0;                                    // row tq of the output block: uniform running pointer
     cdptr wp = cW;                                             // SM: weights of row tq
+    static_assert(RW == 0 || (SM && !RANGED), "the offset forms of the row walk: batch-wide tables, one wave walks every row");
+    constexpr bool ROFF = RW != 0, WUSE = RW == 2;
+    char* const ob = ROFF ? reinterpret_cast<char*>(outb + q0) : nullptr;       // ROFF: uniform base of the output block ...
+    unsigned voff = ROFF ? (unsigned)lane * 8u : 0u;           // ... and the lane's byte offset in row tq (mT * mK * 8 <= 32 KB)
+    const unsigned row_bytes = ROFF ? (unsigned)mK * 8u : 0u;
+    const char IVS_CONST* const wb = ROFF ? reinterpret_cast<const char IVS_CONST*>(cW) : nullptr;
+    unsigned woff = 0;                                         // ROFF: byte offset of row tq's weights
+    auto wld = [&](unsigned off, int k) -> double { return *reinterpret_cast<cdptr>(wb + off + 8 * k); };
     auto put = [&](int row, double v) {                        // row == tq at every call site
         (void)row;
         if (ABL == 4 && (row & 7) != 0) { asm volatile("" :: "v"(v)); return; }
-        if (act) rp[lane] = v;
+        if constexpr (ROFF) { if (act) *reinterpret_cast<double*>(ob + voff) = v; }
+        else if (act) rp[lane] = v;
     };
-    auto adv = [&]() { ++tq; rp += mK; wp += 4; };
+    auto adv = [&]() {
+        if constexpr (ROFF) { voff += row_bytes; woff += 32; }
+        else { ++tq; rp += mK; wp += 4; }
+    };
     auto mine = [&](int row) { return !RANGED || (row >= row_lo && row < row_hi); };      // wave-uniform
     for (int c = 0; c < tt.n_left; ++c, adv()) if (mine(tq)) put(tq, nanv);
     // weights of row tq: LDS broadcast (prefetched one row ahead) when mT <= 16, else readlane
@@ -713,10 +730,17 @@ __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const
     // SM: the next row's weights are requested one row ahead (the table has spare rows behind row mT - 1: TqShared::CP
     // follows W, so the request past the last row needs no clamp).  A wave that skips rows (RANGED) reads at the use.
     double wn0 = 0.0, wn1 = 0.0, wn2 = 0.0, wn3 = 0.0;
-    if (SM && !RANGED) { wn0 = wp[0]; wn1 = wp[1]; wn2 = wp[2]; wn3 = wp[3]; }
+    if constexpr (ROFF && !WUSE) { wn0 = wld(woff, 0); wn1 = wld(woff, 1); wn2 = wld(woff, 2); wn3 = wld(woff, 3); }
+    else if (SM && !RANGED && !WUSE) { wn0 = wp[0]; wn1 = wp[1]; wn2 = wp[2]; wn3 = wp[3]; }
     auto weights = [&](int row, double& a0, double& a1, double& a2, double& a3) {
         (void)row;
-        if (SM && RANGED) {
+        if constexpr (WUSE) {
+            a0 = wld(woff, 0); a1 = wld(woff, 1); a2 = wld(woff, 2); a3 = wld(woff, 3);
+        } else if constexpr (ROFF) {
+            a0 = wn0; a1 = wn1; a2 = wn2; a3 = wn3;
+            asm volatile("" : "+s"(a0), "+s"(a1), "+s"(a2), "+s"(a3));      // as below: out of the counter before the next request
+            wn0 = wld(woff + 32, 0); wn1 = wld(woff + 32, 1); wn2 = wld(woff + 32, 2); wn3 = wld(woff + 32, 3);
+        } else if (SM && RANGED) {
             a0 = wp[0]; a1 = wp[1]; a2 = wp[2]; a3 = wp[3];
         } else if (SM) {
             a0 = wn0; a1 = wn1; a2 = wn2; a3 = wn3;
@@ -909,7 +933,7 @@ __device__ __forceinline__ void dense_maturity_pass(const double (&z)[DT], const
                 const bool slow_iv = !div_safe(tr.y) || !((a == 0.0) || (aa >= 0x1p-500 && aa <= 0x1p500));
                 for (int c = 0; c < n; ++c, adv()) {
                     if (!mine(tq)) continue;
-                    const double xt = SM ? wp[0] : readlane_f64(tt.w0, tq);
+                    const double xt = ROFF ? wld(woff, 0) : SM ? (double)wp[0] : readlane_f64(tt.w0, tq);
                     const double res = slope * (xt - tj.x) + z[jv];
                     const bool slow = slow_iv || __builtin_isnan(res);
                     double r = (tj.x == xt) ? z[jv] : res;

@@ -101,12 +101,23 @@ __device__ __forceinline__ double seg_suffix_prod(double v, int lane) {
     return v;
 }
 
+// LPR ("lane predicates recomputed"): the lane id as the DATA selects and exec masks of a phase see it.  Compares on the
+// plain lane id (lane != 63, seg > 1, seg > 3, seg < 6, lane < 8, ...) are loop invariant: they are hoisted out of the surface
+// loop as 64-bit masks, find no SGPRs there and come back from VGPR spill lanes at every use (two v_readlane and a hazard
+// s_nop for what is one v_cmp).  An opaque copy per phase keeps each compare at its use; addresses (LDS offsets, the
+// lane's column offset) keep the plain lane id and stay hoisted.
+template <bool LPR> __device__ __forceinline__ int pred_lane(int lane) {
+    if (LPR) asm volatile("" : "+v"(lane));
+    return lane;
+}
+
 // K-phase: factorisation tables of the not-a-knot system on n knots (n = KCAP when !VAR) at p_tix(k), the segment
 // products P_j = prod(-AL) / Q_j = prod(-CP) of every 8-knot segment, and from them the multipliers of the carry scans
 // (see pass_sweeps).  Ends with the tables visible to every lane.
-template <int NKB, bool VAR, bool QUADM = false>      // QUADM: the collocation system of the quadratic B-spline instead
+template <int NKB, bool VAR, bool QUADM = false, bool LPR = false>      // QUADM: the collocation system of the quadratic B-spline instead
 __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int lane, double* TB, double* SCR = nullptr) {
     using G = PassGeom<NKB>;
+    const int lp = LPR ? pred_lane<LPR>(lane) : lane;
     constexpr int SL = G::SL, TS = G::TS;
     constexpr int TN = G::TN, NSEG = G::NSEG;
     constexpr bool RUNP = pass_runp<NKB>();         // no PI / PSI tables: segment products go through SCR (free LDS), pm_last behind QQ
@@ -126,7 +137,8 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
         const double xmm = X[i > 1 ? i - 2 : 0];
         const double dxc = xp - x0, dxm = x0 - xm, dxp = xpp - xp, dxmm = xm - xmm;
         const double rdxc = refined_rcp(dxc);
-        const bool first = ir == 0, last = ir == n - 1;
+        const int irp = LPR ? blk * 64 + lp : ir;
+        const bool first = irp == 0, last = irp == n - 1;
         double a, b, c;
         if (QUADM) {
             const CView xv{X, 1};
@@ -139,7 +151,7 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
         const double rb = refined_rcp(b);
         const double crb = c * rb;
         double crb_prev = dpp0_f64<DPP_WAVE_SHR1>(crb);
-        if (blk > 0 && lane == 0) crb_prev = carry_crb;
+        if (blk > 0 && lp == 0) crb_prev = carry_crb;
         const bool ident = first || !in;
         const double g = ident ? 0.0 : a * rb * crb_prev;
         double p00 = 1.0, p01 = ident ? 0.0 : -g, p10 = ident ? 0.0 : 1.0, p11 = ident ? 1.0 : 0.0;
@@ -153,10 +165,10 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
         const double rw = first ? rb : den * rb * refined_rcp(num);
         const double al = a * rw, cp = c * rw;
         double rdx_prev = dpp0_f64<DPP_WAVE_SHR1>(rdxc);
-        if (blk > 0 && lane == 0) rdx_prev = carry_rdx;
+        if (blk > 0 && lp == 0) rdx_prev = carry_rdx;
         const double rdx_next = dpp0_f64<DPP_WAVE_SHL1>(rdxc);          // only row 0 uses it (never crosses a block)
         double rdxmm = dpp0_f64<DPP_WAVE_SHR1>(rdx_prev);
-        if (blk > 0 && lane == 0) rdxmm = carry_rdx_prev;
+        if (blk > 0 && lp == 0) rdxmm = carry_rdx_prev;
         const double d = first ? dxc + dxp : dxmm + dxm;
         const double rd = refined_rcp(d);
         double pm = 0.0, pp, qq;
@@ -175,21 +187,21 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
             pp = 3.0 * dxc * rdx_prev * rw;                      // * dy_{i-1}
             qq = 3.0 * dxm * rdxc * rw;                          // * dy_i
         }
-        const double pi = seg_prefix_prod(in ? -al : 1.0, lane);
-        const double psi = seg_suffix_prod(in ? -cp : 1.0, lane);
+        const double pi = seg_prefix_prod(in ? -al : 1.0, lp);
+        const double psi = seg_suffix_prod(in ? -cp : 1.0, lp);
         {   // beyond n the NEUTRAL row (AL = -1, everything else 0): the forward sweep holds its value, the last system
             // row's CP = 0 cuts the backward recurrence off from whatever lies to its right (see factor_tables_var)
             const int kl = p_tix(ir);
             AL[kl] = in ? al : -1.0; CP[kl] = in ? cp : 0.0; PP[kl] = in ? pp : 0.0; QQ[kl] = in ? qq : 0.0;
             if (RUNP) {
                 if (VAR && last) TB[4 * TN] = pm;
-                if ((lane & (SL - 1)) == SL - 1) SCR[ir / SL] = pi;
-                if ((lane & (SL - 1)) == 0) SCR[NSEG + ir / SL] = in ? psi : 0.0;
+                if ((lp & (SL - 1)) == SL - 1) SCR[ir / SL] = pi;
+                if ((lp & (SL - 1)) == 0) SCR[NSEG + ir / SL] = in ? psi : 0.0;
             } else {
                 if (VAR && last) PI[SL + 1] = pm;      // the third tap exists in the last system row only: one scalar, not a table
                 PI[kl] = pi; PSI[kl] = psi;
-                if ((lane & (SL - 1)) == SL - 1) PI[(ir / SL) * TS + SL] = pi;               // P_j: product of (-AL) over segment j (spare slot)
-                if ((lane & (SL - 1)) == 0) PSI[(ir / SL) * TS + SL] = in ? psi : 0.0;       // Q_j: product of (-CP)
+                if ((lp & (SL - 1)) == SL - 1) PI[(ir / SL) * TS + SL] = pi;               // P_j: product of (-AL) over segment j (spare slot)
+                if ((lp & (SL - 1)) == 0) PSI[(ir / SL) * TS + SL] = in ? psi : 0.0;       // Q_j: product of (-CP)
             }
         }
         if (blk + 1 < NKB) {
@@ -201,18 +213,19 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
     {   // scan multipliers: forward step s (1, 2, 4, 8) multiplies the value 2^s segments to the left by
         // P_j P_{j-1} .. P_{j-s+1}; 0 where no such segment exists (it also silences the DPP sources of the neighbouring
         // row when two rows share a DPP row).  Backward: Q_j .. Q_{j+s-1} and the segment to the right.
-        const int j = lane < NSEG ? lane : NSEG - 1;
-        double pw = lane < NSEG ? (RUNP ? SCR[j] : PI[j * TS + SL]) : 1.0, qw = lane < NSEG ? (RUNP ? SCR[NSEG + j] : PSI[j * TS + SL]) : 1.0;
+        const int j = lane < NSEG ? lane : NSEG - 1;      // addresses
+        const int jp = LPR ? (lp < NSEG ? lp : NSEG - 1) : j;      // selects
+        double pw = lp < NSEG ? (RUNP ? SCR[j] : PI[j * TS + SL]) : 1.0, qw = lp < NSEG ? (RUNP ? SCR[NSEG + j] : PSI[j * TS + SL]) : 1.0;
         double fm[4], bm[4];
 #pragma unroll
         for (int s = 0; s < G::NSCAN; ++s) {
-            fm[s] = j >= (1 << s) ? pw : 0.0;
-            bm[s] = j + (1 << s) <= NSEG - 1 ? qw : 0.0;
+            fm[s] = jp >= (1 << s) ? pw : 0.0;
+            bm[s] = jp + (1 << s) <= NSEG - 1 ? qw : 0.0;
             if (s == 0) { pw *= dpp_f64<DPP_ROW_SHR(1)>(1.0, pw); qw *= dpp_f64<DPP_ROW_SHL(1)>(1.0, qw); }
             if (s == 1) { pw *= dpp_f64<DPP_ROW_SHR(2)>(1.0, pw); qw *= dpp_f64<DPP_ROW_SHL(2)>(1.0, qw); }
             if (s == 2) { pw *= dpp_f64<DPP_ROW_SHR(4)>(1.0, pw); qw *= dpp_f64<DPP_ROW_SHL(4)>(1.0, qw); }
         }
-        if (lane < NSEG) {      // the two spare slots of segment j in the AL / CP / PP / QQ tables
+        if (lp < NSEG) {      // the two spare slots of segment j in the AL / CP / PP / QQ tables
             AL[j * TS + SL] = fm[0]; AL[j * TS + SL + 1] = fm[1]; CP[j * TS + SL] = fm[2];
             PP[j * TS + SL] = bm[0]; PP[j * TS + SL + 1] = bm[1]; QQ[j * TS + SL] = bm[2];
             if (NSEG > 8) { CP[j * TS + SL + 1] = fm[3]; QQ[j * TS + SL + 1] = bm[3]; }
@@ -222,7 +235,7 @@ __device__ __forceinline__ void pass_factor_tables(const double* X, int n, int l
 }
 
 // One pass: slopes of the RP rows staged in Yp -> Sp.  All 64 lanes; no barrier inside (the caller brackets it).
-template <int NKB, bool VAR, bool QUADM = false>
+template <int NKB, bool VAR, bool QUADM = false, bool LPR = false>
 __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const double* TB, int lane, int n) {
     using G = PassGeom<NKB>;
     constexpr int SL = G::SL, TN = G::TN, NSEG = G::NSEG, RS = G::RS, TS = G::TS;
@@ -232,7 +245,8 @@ __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const 
     const double pm_last = VAR ? (RUNP ? TB[4 * TN] : PI[SL + 1]) : 0.0;  // run-time n: third tap of the last system row (wave-uniform)
     const int tl = lane / NSEG, seg = lane % NSEG;
     const int kb = seg * SL, tb = seg * TS;
-    const bool s_first = seg == 0, s_last = seg == NSEG - 1;
+    const int segp = LPR ? pred_lane<LPR>(lane) % NSEG : seg;
+    const bool s_first = segp == 0, s_last = segp == NSEG - 1;      // data selects; the address select below keeps the plain lane id
     const int mlast = n - 1 - kb;                   // position of the last system row in this lane's segment (VAR)
     const double* yr = Yp + tl * RS + kb;
     const int fy = NKB == 2 ? (seg >> 2) & 3 : 0;   // slot swizzle of this segment in the Y plane
@@ -244,7 +258,7 @@ __device__ __forceinline__ void pass_sweeps(const double* Yp, double* Sp, const 
     }
     {   // the two knots to the left (segment 0: re-reads its own first pair, selected away / multiplied by 0 below)
         const int fl = NKB == 2 ? ((seg - 1) >> 2) & 3 : 0;
-        const double2 v = *reinterpret_cast<const double2*>(s_first ? yr : yr - SL + 2 * ((SL / 2 - 1) ^ fl));
+        const double2 v = *reinterpret_cast<const double2*>(seg == 0 ? yr : yr - SL + 2 * ((SL / 2 - 1) ^ fl));
         y[0] = v.x; y[1] = v.y;
     }
     {   // first knot of the next segment (last segment: the spare slot behind the row / the next row's first entry)
@@ -467,7 +481,14 @@ __device__ unsigned long long* d_pass_ends = nullptr;
 // strike search and at the loop top.  Instantiated where it measured a gain: the fixed 64 x 16 kernels of
 // every method but the step rules (nearest / zero / from_derivatives lost 0.9 % with it) and the NT16 kernels of
 // linear / slinear (+3.3 % on config 5; cubic did not move there, pchip lost 2.6 %).
-template <int METHOD, int NKB, bool VAR, bool TSH = true, bool NT16 = false, bool KQS = false>
+// RW: less bookkeeping per surface: a wave issues in order, three waves share a SIMD, and every scalar move or
+// spill-lane read costs the issue slot an FMA would have taken.  Bit 0 = LPR (pred_lane: the K-phase and the sweeps recompute
+// their lane predicates instead of reading hoisted masks back from spill lanes; inert for the methods without sweeps),
+// RW >> 1 = the row walk of the maturity pass (dense_maturity_pass's RW; 2 = one running 32-bit offset per stream and the
+// row's weights loaded at the use).  RW = 5 on the fixed shared-grid cubic kernel: 75 -> 31 SGPR spills, 217 of the surface
+// loop's 1918 static instructions gone, outputs bit-identical, 2.2-2.9 % faster on three devices; instantiated where it
+// measured a gain: cubic, cubicspline, quadratic (5), pchip, akima (4).  RW = 0 compiles to the code of before.
+template <int METHOD, int NKB, bool VAR, bool TSH = true, bool NT16 = false, bool KQS = false, int RW = 0>
 // Wavefronts per SIMD: 3 (168 VGPRs); the run-time-maturity-count instantiations of pchip / akima need ~200 (the per-lane
 // maturity solve of the local rules) and run at 2 without scratch -- at 3 they spilled 14-36 registers and lost 3-30 %.
 // Their NT16 forms fit 3: pchip 161 VGPRs (48 B of scratch at 65..128 strikes), akima 164 / 166 with the rolling maturity slopes.
@@ -652,7 +673,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
             if (ok) {
                 if (ps == 0 && !same_k) {
                     if (LOCAL) pass_local_tables<NKB, VAR>(Ksh, n, lane, TB);
-                    else if (!LERP && ABL != 1 && ABL != 6) pass_factor_tables<NKB, VAR, QUADK>(Ksh, n, lane, TB, Sp + KCAP);
+                    else if (!LERP && ABL != 1 && ABL != 6) pass_factor_tables<NKB, VAR, QUADK, (RW & 1) != 0>(Ksh, n, lane, TB, Sp + KCAP);
                 }
                 if (ps == 0 && !(same_k && kq_shared)) {
                     // ---- strike search + weights of this lane's output strike (once per strike grid / query grid)
@@ -712,7 +733,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
                     continue;
                 }
                 if (LOCAL) pass_local_slopes<METHOD, NKB, VAR>(Yp, Sp, TB, lane, n);
-                else if (ABL != 1 && ABL != 6) pass_sweeps<NKB, VAR, QUADK>(Yp, Sp, TB, lane, n);
+                else if (ABL != 1 && ABL != 6) pass_sweeps<NKB, VAR, QUADK, (RW & 1) != 0>(Yp, Sp, TB, lane, n);
                 __syncthreads();
                 // ---- strike evaluation of the pass's rows (q-lane), gathers pipelined LA rows ahead
                 if (ABL == 2 || ABL == 6) {
@@ -748,7 +769,7 @@ void surface_pass_kernel(SurfaceParams p, VarList list) {
 #pragma unroll
                 for (int r = 0; r < DT; ++r) asm volatile("" : "+v"(z[r]));      // see dense_maturity_pass
             }
-            if (act) dense_maturity_pass<METHOD, true, false, NTR, TSH>(z, tt, TSH ? TTp : TTl, TSH ? Wp : Wl, outb, 0, lane, true, mT, mK,
+            if (act) dense_maturity_pass<METHOD, true, false, NTR, TSH, (RW >> 1)>(z, tt, TSH ? TTp : TTl, TSH ? Wp : Wl, outb, 0, lane, true, mT, mK,
                                                                         nostamp, 0, 0, nT);
             if (p.status && lane == 0) p.status[b] = IVS_ST_OK;
         } else if (lane == 0) {
@@ -812,7 +833,10 @@ inline int launch_surface_pass(const SurfaceParams& p_in, const LaunchCtx& cx, c
             constexpr bool KQS_OK = VAR ? N16 && (M == IVS_LINEAR || M == IVS_SLINEAR) : !d_is_step(M);
             with_bool(KQS_OK && p.kq_stride == 0, [&](auto k) {
                 constexpr bool KQS = KQS_OK && decltype(k)::value;
-                hipLaunchKernelGGL((surface_pass_kernel<M, NKB, VAR, true, N16, KQS>), dim3((unsigned)grid), dim3(64), lds, cx.st, p, list);
+                // ... and the leaner bookkeeping (see RW) where that measured a gain: the fixed shared-grid kernels of the
+                // methods with slopes.  linear / slinear stayed inside the noise with it and keep the old row walk.
+                constexpr int RWF = !(!VAR && KQS) ? 0 : (d_is_nak(M) || d_is_quad(M)) ? 5 : d_is_local(M) ? 4 : 0;
+                hipLaunchKernelGGL((surface_pass_kernel<M, NKB, VAR, true, N16, KQS, RWF>),dim3((unsigned)grid), dim3(64), lds, cx.st, p, list);
             });
         });
     };
