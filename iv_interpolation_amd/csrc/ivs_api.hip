@@ -76,6 +76,58 @@ void current_device(int& dev, int& cus) {
 }
 int num_cu() { int d, c; current_device(d, c); return c; }
 
+// ---- the checks and launch steps the snapshot-analytics calls (ivs_*_args) share; each returns IVS_OK or the failure
+
+// opens a call: no error, no kernel yet.  None of these calls takes device scratch, so their workspace arguments go unnamed.
+int begin_call(const char* fn, const void* args) {
+    g_err[0] = 0;
+    g_last_kernel = "";
+    return args ? IVS_OK : fail(IVS_EINVAL, "%s: null args", fn);
+}
+
+// closes a call after its one launch
+int end_call(const char* kernel) {
+    g_last_kernel = kernel;
+    return check_launch(kernel);
+}
+
+// a query grid is shared by all surfaces (stride 0) or dense per surface (stride = its length)
+int check_grid_stride(const char* fn, int64_t stride, int64_t len) {
+    return stride == 0 || stride == len ? IVS_OK : fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+}
+
+// B x mT rows are indexed, and spread over a grid, as int32
+int check_rows(const char* fn, int64_t B, int32_t mT) {
+    return B > 0x7fffffffLL / mT ? fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)B, mT) : IVS_OK;
+}
+
+// rows per wavefront of the kernels whose inversion phase packs several rows into one wavefront: fill its 64 lanes (`cap`
+// rows do), but keep ~16 wavefronts per CU while the batch is small; `forced` > 0 is the tuning / testing override
+int32_t rows_per_wave(int64_t rows, int cap, int forced) {
+    int dev, cus;
+    current_device(dev, cus);
+    int64_t group = rows / ((int64_t)cus * 16);
+    group = group < 1 ? 1 : (group > cap ? cap : group);
+    return (int32_t)(forced > 0 ? forced : group);
+}
+
+// ivs_svi_eval_f64, ivs_svi_greeks_f64, ivs_svi_book_f64: the shape of B snapshots of mT slices and Q queries / options each
+int check_query_shape(const char* fn, int64_t B, int32_t mT, int64_t Q, int64_t tq_stride, int64_t q_stride, int32_t strike_mode) {
+    if (B < 0 || mT < 0 || Q < 0 || tq_stride < 0 || q_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (strike_mode != 0 && strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, strike_mode);
+    if (mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, mT, ivs::ST_MAX_T);
+    return IVS_OK;
+}
+
+// ... and, for a batch that is not empty, their strides and launch limits; `noun` is what the call names its Q entries
+int check_query_launch(const char* fn, const char* noun, int64_t B, int32_t mT, int64_t Q, int64_t tq_stride, int64_t q_stride) {
+    if ((tq_stride != 0 && tq_stride != mT) || (q_stride != 0 && q_stride != Q))
+        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
+    if (int rc = check_rows(fn, B, mT)) return rc;
+    if (B > 0x7fffffffLL / Q) return fail(IVS_ERANGE, "%s: %lld x %lld %s exceed one launch", fn, (long long)B, (long long)Q, noun);
+    return IVS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -328,12 +380,9 @@ int ivs_frame_columns_f64(const ivs_frame_args* a, void* workspace, size_t works
     return check_launch("frame_fused_kernel");
 }
 
-int ivs_snapshot_assemble_f64(const ivs_snapshot_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_snapshot_assemble_f64(const ivs_snapshot_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_snapshot_assemble_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->n_rows < 0 || a->n_contracts < 0 || a->nT < 0 || a->nK < 0 || a->n_snapshots < 0 || a->mK < 0)
         return fail(IVS_EINVAL, "%s: negative size", fn);
     if (a->nT > 32) return fail(IVS_ERANGE, "%s: nT=%d expiries exceed the surface engine's 32", fn, a->nT);
@@ -365,16 +414,12 @@ int ivs_snapshot_assemble_f64(const ivs_snapshot_args* a, void* workspace, size_
     p.sigma = a->sigma; p.T = a->T; p.spot = a->spot; p.quotes = a->quotes; p.Kq = a->Kq;
     hipLaunchKernelGGL(ivs::snapshot_assemble_kernel, dim3((unsigned)n_tiles), dim3((unsigned)(waves * 64)), 0,
                        static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "snapshot_assemble_kernel";
-    return check_launch("snapshot_assemble_kernel");
+    return end_call("snapshot_assemble_kernel");
 }
 
-int ivs_smile_delta_points_f64(const ivs_smile_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_smile_delta_points_f64(const ivs_smile_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_smile_delta_points_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
     if (a->nD < 1 || a->nD > ivs::SM_MAX_D) return fail(IVS_ERANGE, "%s: nD=%d outside [1,%d]", fn, a->nD, ivs::SM_MAX_D);
     if (a->mK < 2) return fail(IVS_ERANGE, "%s: mK=%d < 2: a bracket needs two nodes", fn, a->mK);
@@ -385,44 +430,32 @@ int ivs_smile_delta_points_f64(const ivs_smile_args* a, void* workspace, size_t 
         return fail(IVS_EINVAL, "%s: null pointer", fn);
     if ((a->kq_stride != 0 && a->kq_stride < a->mK) || (a->tq_stride != 0 && a->tq_stride < a->mT))
         return fail(IVS_EINVAL, "%s: grid stride smaller than the grid", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (int rc = check_rows(fn, a->B, a->mT)) return rc;
     ivs::SmileParams p{};
     p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
     p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate;
     for (int t = 0; t < a->nD; ++t) p.z[t] = a->z[t];
     p.mK = a->mK; p.mT = a->mT; p.nD = a->nD; p.rows = a->B * a->mT;
     p.q_vol = a->q_vol; p.q_strike = a->q_strike; p.q_flags = a->q_flags;
-    // rows per wavefront: fill the 64 lanes of the inversion phase, but keep ~16 wavefronts per CU while the batch is small
-    int dev, cus;
-    current_device(dev, cus);
-    int64_t group = p.rows / ((int64_t)cus * 16);
-    group = group < 1 ? 1 : (group > 64 / a->nD ? 64 / a->nD : group);
-    if (a->rows_per_wave > 0) group = a->rows_per_wave;     // tuning / testing override
-    p.group = (int32_t)group;
-    const int64_t waves = (p.rows + group - 1) / group;
+    p.group = rows_per_wave(p.rows, 64 / a->nD, a->rows_per_wave);
+    const int64_t waves = (p.rows + p.group - 1) / p.group;
     hipLaunchKernelGGL(ivs::smile_delta_kernel, dim3((unsigned)((waves + ivs::SM_WAVES - 1) / ivs::SM_WAVES)),
                        dim3(ivs::SM_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "smile_delta_kernel";
-    return check_launch("smile_delta_kernel");
+    return end_call("smile_delta_kernel");
 }
 
-int ivs_surface_arbitrage_f64(const ivs_arbitrage_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_surface_arbitrage_f64(const ivs_arbitrage_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_surface_arbitrage_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
     if (a->mK < 3) return fail(IVS_ERANGE, "%s: mK=%d < 3: the strike stencil needs three nodes", fn, a->mK);
     if (a->mT < 2) return fail(IVS_ERANGE, "%s: mT=%d < 2: the tenor stencil needs two rows", fn, a->mT);
     if (a->B == 0) return IVS_OK;
     if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->flags || !a->counts || !a->worst)
         return fail(IVS_EINVAL, "%s: null pointer", fn);
-    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
-        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (int rc = check_grid_stride(fn, a->kq_stride, a->mK)) return rc;
+    if (int rc = check_grid_stride(fn, a->tq_stride, a->mT)) return rc;
+    if (int rc = check_rows(fn, a->B, a->mT)) return rc;
     ivs::ArbParams p{};
     p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
     p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate;
@@ -446,16 +479,12 @@ int ivs_surface_arbitrage_f64(const ivs_arbitrage_args* a, void* workspace, size
     const int64_t grid = (a->B + p.spw - 1) / p.spw;
     hipLaunchKernelGGL(ivs::surface_arbitrage_kernel, dim3((unsigned)grid), dim3(ivs::AR_WAVES * 64), 0,
                        static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "surface_arbitrage_kernel";
-    return check_launch("surface_arbitrage_kernel");
+    return end_call("surface_arbitrage_kernel");
 }
 
-int ivs_surface_moments_f64(const ivs_moments_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_surface_moments_f64(const ivs_moments_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_surface_moments_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->nH < 0 || a->kq_stride < 0 || a->tq_stride < 0)
         return fail(IVS_EINVAL, "%s: negative size", fn);
     if (a->mK < 2) return fail(IVS_ERANGE, "%s: mK=%d < 2: a segment needs two nodes", fn, a->mK);
@@ -471,10 +500,9 @@ int ivs_surface_moments_f64(const ivs_moments_args* a, void* workspace, size_t w
     if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->raw || !a->stats || !a->mass || !a->flags)
         return fail(IVS_EINVAL, "%s: null pointer", fn);
     if (a->nH > 0 && (!a->index || !a->index_flags)) return fail(IVS_EINVAL, "%s: null index / index_flags with nH=%d", fn, a->nH);
-    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
-        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (int rc = check_grid_stride(fn, a->kq_stride, a->mK)) return rc;
+    if (int rc = check_grid_stride(fn, a->tq_stride, a->mT)) return rc;
+    if (int rc = check_rows(fn, a->B, a->mT)) return rc;
     if (a->mT > ivs::MM_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d row slots per snapshot", fn, a->mT, ivs::MM_MAX_T);
     ivs::MomParams p{};
     p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
@@ -491,16 +519,12 @@ int ivs_surface_moments_f64(const ivs_moments_args* a, void* workspace, size_t w
     const size_t lds = (size_t)spw * a->mT * sizeof(ivs::MomSlot);
     hipLaunchKernelGGL(ivs::surface_moments_kernel, dim3((unsigned)grid), dim3(ivs::MM_WAVES * 64), lds,
                        static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "surface_moments_kernel";
-    return check_launch("surface_moments_kernel");
+    return end_call("surface_moments_kernel");
 }
 
-int ivs_svi_slices_f64(const ivs_svi_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_svi_slices_f64(const ivs_svi_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_svi_slices_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
     if (a->mK < 5) return fail(IVS_ERANGE, "%s: mK=%d < 5: five parameters need five nodes", fn, a->mK);
     if (a->mK > ivs::SV_MAX_K) return fail(IVS_ERANGE, "%s: mK=%d > %d nodes of the LDS slot", fn, a->mK, ivs::SV_MAX_K);
@@ -511,10 +535,9 @@ int ivs_svi_slices_f64(const ivs_svi_args* a, void* workspace, size_t workspace_
     if (a->B == 0 || a->mT == 0) return IVS_OK;
     if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->params || !a->fit || !a->flags)
         return fail(IVS_EINVAL, "%s: null pointer", fn);
-    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
-        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (int rc = check_grid_stride(fn, a->kq_stride, a->mK)) return rc;
+    if (int rc = check_grid_stride(fn, a->tq_stride, a->mT)) return rc;
+    if (int rc = check_rows(fn, a->B, a->mT)) return rc;
     ivs::SviParams p{};
     p.vol = a->vol; p.Kq = a->Kq; p.Tq = a->Tq; p.spot = a->spot;
     p.kq_stride = a->kq_stride; p.tq_stride = a->tq_stride; p.rate = a->rate;
@@ -531,16 +554,12 @@ int ivs_svi_slices_f64(const ivs_svi_args* a, void* workspace, size_t workspace_
     const size_t lds = (size_t)rpw * a->mK * 16;
     hipLaunchKernelGGL(ivs::svi_slice_kernel, dim3((unsigned)grid), dim3(ivs::SV_WAVES * 64), lds,
                        static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "svi_slice_kernel";
-    return check_launch("svi_slice_kernel");
+    return end_call("svi_slice_kernel");
 }
 
-int ivs_svi_distribution_f64(const ivs_distribution_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_svi_distribution_f64(const ivs_distribution_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_svi_distribution_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->B < 0 || a->mT < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
     if (a->nP < 1 || a->nP > ivs::DS_MAX_P) return fail(IVS_ERANGE, "%s: nP=%d outside [1,%d]", fn, a->nP, ivs::DS_MAX_P);
     if (a->nL < 0 || a->nL > ivs::DS_MAX_L) return fail(IVS_ERANGE, "%s: nL=%d outside [0,%d]", fn, a->nL, ivs::DS_MAX_L);
@@ -559,9 +578,8 @@ int ivs_svi_distribution_f64(const ivs_distribution_args* a, void* workspace, si
     if (!a->params || !a->Tq || !a->spot || !a->q_x || !a->q_strike || !a->q_flags || !a->tails || !a->flags)
         return fail(IVS_EINVAL, "%s: null pointer", fn);
     if (a->nL > 0 && (!a->p_below || !a->p_above)) return fail(IVS_EINVAL, "%s: null p_below / p_above with nL=%d", fn, a->nL);
-    if (a->tq_stride != 0 && a->tq_stride != a->mT) return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (int rc = check_grid_stride(fn, a->tq_stride, a->mT)) return rc;
+    if (int rc = check_rows(fn, a->B, a->mT)) return rc;
     ivs::DistParams p{};
     p.params = a->params; p.Tq = a->Tq; p.spot = a->spot;
     p.tq_stride = a->tq_stride; p.rate = a->rate; p.max_tail = a->max_tail;
@@ -571,26 +589,16 @@ int ivs_svi_distribution_f64(const ivs_distribution_args* a, void* workspace, si
     p.q_x = a->q_x; p.q_strike = a->q_strike; p.q_flags = a->q_flags;
     p.p_below = a->nL > 0 ? a->p_below : nullptr; p.p_above = a->nL > 0 ? a->p_above : nullptr;
     p.tails = a->tails; p.flags = a->flags;
-    // rows per wavefront: fill the 64 lanes of the inversion phase, but keep ~16 wavefronts per CU while the batch is small
-    int dev, cus;
-    current_device(dev, cus);
-    int64_t group = p.rows / ((int64_t)cus * 16);
-    group = group < 1 ? 1 : (group > 64 / a->nP ? 64 / a->nP : group);
-    if (a->rows_per_wave > 0) group = a->rows_per_wave;     // tuning / testing override
-    p.group = (int32_t)group;
-    const int64_t waves = (p.rows + group - 1) / group;
+    p.group = rows_per_wave(p.rows, 64 / a->nP, a->rows_per_wave);
+    const int64_t waves = (p.rows + p.group - 1) / p.group;
     hipLaunchKernelGGL(ivs::svi_distribution_kernel, dim3((unsigned)((waves + ivs::DS_WAVES - 1) / ivs::DS_WAVES)),
                        dim3(ivs::DS_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "svi_distribution_kernel";
-    return check_launch("svi_distribution_kernel");
+    return end_call("svi_distribution_kernel");
 }
 
-int ivs_svi_calendar_f64(const ivs_calendar_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_svi_calendar_f64(const ivs_calendar_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_svi_calendar_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->B < 0 || a->mT < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
     if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one ballot", fn, a->mT, ivs::ST_MAX_T);
     if (a->rows_per_wave < 0 || a->rows_per_wave > ivs::SC_MAX_GROUP)
@@ -598,45 +606,27 @@ int ivs_svi_calendar_f64(const ivs_calendar_args* a, void* workspace, size_t wor
     if (a->B == 0 || a->mT == 0) return IVS_OK;
     if (!a->params || !a->Tq || !a->spot || !a->d_min || !a->x_min || !a->d_atm || !a->x_cross || !a->n_cross || !a->flags)
         return fail(IVS_EINVAL, "%s: null pointer", fn);
-    if (a->tq_stride != 0 && a->tq_stride != a->mT) return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
+    if (int rc = check_grid_stride(fn, a->tq_stride, a->mT)) return rc;
+    if (int rc = check_rows(fn, a->B, a->mT)) return rc;
     ivs::CalParams p{};
     p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.tq_stride = a->tq_stride;
     p.mT = a->mT; p.rows = a->B * a->mT;
     p.d_min = a->d_min; p.x_min = a->x_min; p.d_atm = a->d_atm; p.x_cross = a->x_cross;
     p.n_cross = a->n_cross; p.flags = a->flags;
-    // rows per wavefront: fill the 64 lanes of the inversion phase, but keep ~16 wavefronts per CU while the batch is small
-    int dev, cus;
-    current_device(dev, cus);
-    int64_t group = p.rows / ((int64_t)cus * 16);
-    group = group < 1 ? 1 : (group > ivs::SC_MAX_GROUP ? ivs::SC_MAX_GROUP : group);
-    if (a->rows_per_wave > 0) group = a->rows_per_wave;     // tuning / testing override
-    p.group = (int32_t)group;
-    const int64_t waves = (p.rows + group - 1) / group;
+    p.group = rows_per_wave(p.rows, ivs::SC_MAX_GROUP, a->rows_per_wave);
+    const int64_t waves = (p.rows + p.group - 1) / p.group;
     hipLaunchKernelGGL(ivs::svi_calendar_kernel, dim3((unsigned)((waves + ivs::SC_WAVES - 1) / ivs::SC_WAVES)),
                        dim3(ivs::SC_WAVES * 64), 0, static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "svi_calendar_kernel";
-    return check_launch("svi_calendar_kernel");
+    return end_call("svi_calendar_kernel");
 }
 
-int ivs_svi_eval_f64(const ivs_eval_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_svi_eval_f64(const ivs_eval_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_svi_eval_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
-    if (a->B < 0 || a->mT < 0 || a->Q < 0 || a->tq_stride < 0 || a->q_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
-    if (a->strike_mode != 0 && a->strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, a->strike_mode);
-    if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, a->mT, ivs::ST_MAX_T);
+    if (int rc = begin_call(fn, a)) return rc;
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->Q, a->tq_stride, a->q_stride, a->strike_mode)) return rc;
     if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;
     if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->flags) return fail(IVS_EINVAL, "%s: null pointer", fn);
-    if ((a->tq_stride != 0 && a->tq_stride != a->mT) || (a->q_stride != 0 && a->q_stride != a->Q))
-        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
-    if (a->B > 0x7fffffffLL / a->Q)
-        return fail(IVS_ERANGE, "%s: %lld x %lld queries exceed one launch", fn, (long long)a->B, (long long)a->Q);
+    if (int rc = check_query_launch(fn, "queries", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
     ivs::EvalParams p{};
     p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau;
     p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
@@ -646,27 +636,16 @@ int ivs_svi_eval_f64(const ivs_eval_args* a, void* workspace, size_t workspace_b
     p.flags = a->flags;
     const int64_t grid = a->B * p.nqb;                      // <= B * Q < 2^31
     hipLaunchKernelGGL(ivs::svi_eval_kernel, dim3((unsigned)grid), dim3(ivs::SE_BLOCK), 0, static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "svi_eval_kernel";
-    return check_launch("svi_eval_kernel");
+    return end_call("svi_eval_kernel");
 }
 
-int ivs_svi_greeks_f64(const ivs_greeks_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_svi_greeks_f64(const ivs_greeks_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_svi_greeks_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
-    if (a->B < 0 || a->mT < 0 || a->Q < 0 || a->tq_stride < 0 || a->q_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
-    if (a->strike_mode != 0 && a->strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, a->strike_mode);
-    if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, a->mT, ivs::ST_MAX_T);
+    if (int rc = begin_call(fn, a)) return rc;
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->Q, a->tq_stride, a->q_stride, a->strike_mode)) return rc;
     if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;
     if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->flags) return fail(IVS_EINVAL, "%s: null pointer", fn);
-    if ((a->tq_stride != 0 && a->tq_stride != a->mT) || (a->q_stride != 0 && a->q_stride != a->Q))
-        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
-    if (a->B > 0x7fffffffLL / a->Q)
-        return fail(IVS_ERANGE, "%s: %lld x %lld options exceed one launch", fn, (long long)a->B, (long long)a->Q);
+    if (int rc = check_query_launch(fn, "options", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
     ivs::RiskParams p{};
     p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put;
     p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
@@ -677,20 +656,14 @@ int ivs_svi_greeks_f64(const ivs_greeks_args* a, void* workspace, size_t workspa
     p.flags = a->flags;
     const int64_t grid = a->B * p.nqb;                      // <= B * Q < 2^31
     hipLaunchKernelGGL(ivs::svi_greeks_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "svi_greeks_kernel";
-    return check_launch("svi_greeks_kernel");
+    return end_call("svi_greeks_kernel");
 }
 
-int ivs_svi_book_f64(const ivs_book_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_svi_book_f64(const ivs_book_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_svi_book_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
-    if (a->B < 0 || a->mT < 0 || a->Q < 0 || a->nA < 0 || a->nV < 0 || a->tq_stride < 0 || a->q_stride < 0)
-        return fail(IVS_EINVAL, "%s: negative size", fn);
-    if (a->strike_mode != 0 && a->strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, a->strike_mode);
-    if (a->mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, a->mT, ivs::ST_MAX_T);
+    if (int rc = begin_call(fn, a)) return rc;
+    if (a->nA < 0 || a->nV < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->Q, a->tq_stride, a->q_stride, a->strike_mode)) return rc;
     if (a->nA > ivs::RK_MAX_SHOCKS || a->nV > ivs::RK_MAX_SHOCKS)
         return fail(IVS_ERANGE, "%s: nA=%d or nV=%d > %d shocks per axis", fn, a->nA, a->nV, ivs::RK_MAX_SHOCKS);
     if (a->nA * a->nV > ivs::RK_MAX_GRID) return fail(IVS_ERANGE, "%s: nA*nV=%d > %d cells", fn, a->nA * a->nV, ivs::RK_MAX_GRID);
@@ -707,12 +680,7 @@ int ivs_svi_book_f64(const ivs_book_args* a, void* workspace, size_t workspace_b
     if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;
     if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->qty || !a->net || !a->n_dead) return fail(IVS_EINVAL, "%s: null pointer", fn);
     if (ncell > 0 && !a->cell_flags) return fail(IVS_EINVAL, "%s: null pointer (cell_flags)", fn);
-    if ((a->tq_stride != 0 && a->tq_stride != a->mT) || (a->q_stride != 0 && a->q_stride != a->Q))
-        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
-    if (a->B > 0x7fffffffLL / a->mT)
-        return fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)a->B, a->mT);
-    if (a->B > 0x7fffffffLL / a->Q)
-        return fail(IVS_ERANGE, "%s: %lld x %lld options exceed one launch", fn, (long long)a->B, (long long)a->Q);
+    if (int rc = check_query_launch(fn, "options", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
     if (ncell > 0 && a->B > 0x7fffffffLL / ncell)
         return fail(IVS_ERANGE, "%s: %lld x %d cells exceed one launch", fn, (long long)a->B, ncell);
     ivs::BookParams p{};
@@ -738,16 +706,12 @@ int ivs_svi_book_f64(const ivs_book_args* a, void* workspace, size_t workspace_b
     p.cpb = cpb; p.nchunk = nchunk;
     const int64_t grid = a->B * nchunk;                     // <= B * max(ncell, 1) < 2^31
     hipLaunchKernelGGL(ivs::svi_book_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "svi_book_kernel";
-    return check_launch("svi_book_kernel");
+    return end_call("svi_book_kernel");
 }
 
-int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_ssvi_surface_f64";
-    (void)workspace; (void)workspace_bytes;                 // no device scratch
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
+    if (int rc = begin_call(fn, a)) return rc;
     if (a->B < 0 || a->mT < 0 || a->mK < 0 || a->kq_stride < 0 || a->tq_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
     if ((a->raw != nullptr) == (a->theta0 != nullptr))
         return fail(IVS_EINVAL, "%s: exactly one of raw and theta0 must be given", fn);
@@ -760,8 +724,8 @@ int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void* workspace, size_t workspa
     if (a->B == 0 || a->mT == 0) return IVS_OK;
     if (!a->vol || !a->Kq || !a->Tq || !a->spot || !a->surface || !a->theta || !a->params || !a->fit || !a->flags || !a->sflags)
         return fail(IVS_EINVAL, "%s: null pointer", fn);
-    if ((a->kq_stride != 0 && a->kq_stride != a->mK) || (a->tq_stride != 0 && a->tq_stride != a->mT))
-        return fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
+    if (int rc = check_grid_stride(fn, a->kq_stride, a->mK)) return rc;
+    if (int rc = check_grid_stride(fn, a->tq_stride, a->mT)) return rc;
     if (a->B > 0x7fffffffLL / ((int64_t)a->mT * a->mK))
         return fail(IVS_ERANGE, "%s: %lld x %d x %d nodes exceed one launch", fn, (long long)a->B, a->mT, a->mK);
     ivs::SsviParams p{};
@@ -774,8 +738,7 @@ int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void* workspace, size_t workspa
     const size_t lds = (size_t)a->mT * a->mK * 16;          // one workgroup per snapshot, its valid nodes in LDS
     hipLaunchKernelGGL(ivs::ssvi_surface_kernel, dim3((unsigned)a->B), dim3(ivs::SS_THREADS), lds,
                        static_cast<hipStream_t>(stream), p);
-    g_last_kernel = "ssvi_surface_kernel";
-    return check_launch("ssvi_surface_kernel");
+    return end_call("ssvi_surface_kernel");
 }
 
 int ivs_candle_aggregate_f64(const int64_t* ts_ns, const double* open, const double* high, const double* low,

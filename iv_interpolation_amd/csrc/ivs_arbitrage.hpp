@@ -31,8 +31,6 @@ struct ArbParams {
 
 struct ArbSlot { int32_t c[4]; double mn[2]; };
 
-__device__ __forceinline__ bool ar_pos(double v) { return v > 0.0 && v < __builtin_inf(); }   // finite and > 0
-
 // 3-point first-derivative weights on the spacings hm (to the left) and hp (to the right), rule A3
 __device__ __forceinline__ void ar_d1_weights(double hm, double hp, double& am, double& a0, double& ap) {
     am = -hp / (hm * (hm + hp));
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(AR_WAVES * 64) void surface_arbitrage_kernel(ArbPar
         const int j0 = strip * p.strip;
         const int j1 = j0 + p.strip < p.mT ? j0 + p.strip : p.mT;
         const double S = p.spot[b];
-        const bool s_ok = ar_pos(S);
+        const bool s_ok = finite_pos(S);
         const double* kr = p.Kq + b * p.kq_stride;
         const double* tq = p.Tq + b * p.tq_stride;
         const double* vb = p.vol + b * (int64_t)p.mT * p.mK;
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(AR_WAVES * 64) void surface_arbitrage_kernel(ArbPar
         const double k = in ? kr[i] : qnan();
         const double km = (in && i > 0) ? kr[i - 1] : qnan();
         const double kp = (i + 1 < p.mK) ? kr[i + 1] : qnan();
-        const bool kv = ar_pos(k), kvm = ar_pos(km), kvp = ar_pos(kp);
+        const bool kv = finite_pos(k), kvm = finite_pos(km), kvp = finite_pos(kp);
         const double hm = log1p((k - km) / km), hp = log1p((kp - k) / k);
         const bool k_stencil = kv && kvm && kvp && hm > 0.0 && hp > 0.0;
         double am, a0, ap;
@@ -103,20 +101,20 @@ __global__ __launch_bounds__(AR_WAVES * 64) void surface_arbitrage_kernel(ArbPar
         double mnN = __builtin_inf(), mnG = __builtin_inf();
         for (int j = j0; j < j1; ++j) {
             load_row(j + 2, s_f, h_f, t_f);
-            const bool live = s_ok && ar_pos(t_c);                        // A1
-            const bool valid = live && kv && ar_pos(s_c);
+            const bool live = s_ok && finite_pos(t_c);                    // A1
+            const bool valid = live && kv && finite_pos(s_c);
             const double w = s_c * s_c * t_c;                             // A2
             // A3: strike neighbours by lane shifts, the chunk's edges from the halo
             double sm = __shfl_up(s_c, 1), sp = __shfl_down(s_c, 1);
             if (lane == 0) sm = h_c;
             if (lane == 63) sp = h_c;
-            const bool st_k = k_stencil && ar_pos(sm) && ar_pos(sp);
+            const bool st_k = k_stencil && finite_pos(sm) && finite_pos(sp);
             const double wm = sm * sm * t_c, wp = sp * sp * t_c;
             const double w1 = am * wm + a0 * w + ap * wp;
             const double w2 = bm * wm + bc * w + bp * wp;
             // A4: tenor neighbours at the same strike
-            const bool up = s_ok && ar_pos(t_n) && t_n > t_c && kv && ar_pos(s_n);
-            const bool dn = s_ok && ar_pos(t_p) && t_p < t_c && kv && ar_pos(s_p);
+            const bool up = s_ok && finite_pos(t_n) && t_n > t_c && kv && finite_pos(s_n);
+            const bool dn = s_ok && finite_pos(t_p) && t_p < t_c && kv && finite_pos(s_p);
             const double wu = s_n * s_n * t_n, wd = s_p * s_p * t_p;
             const double dm = t_c - t_p, dp = t_n - t_c;
             double cm, cc, cp;

@@ -15,6 +15,10 @@ constexpr int WAVE = 64;
 
 __device__ __forceinline__ double qnan() { return __builtin_nan(""); }
 
+// the liveness tests of the snapshot analytics; both are false for NaN
+__device__ __forceinline__ bool finite_pos(double v) { return v > 0.0 && v < __builtin_inf(); }      // finite and > 0
+__device__ __forceinline__ bool is_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
+
 // the standard normal's distribution function and density, shared by every kernel that prices or differentiates
 __device__ __forceinline__ double norm_cdf(double x) { return 0.5 * erfc(-x * 0.70710678118654752440); }
 __device__ __forceinline__ double norm_pdf(double x) { return exp(-x * x * 0.5) * 0.39894228040143267794; }

@@ -37,12 +37,11 @@ struct DistParams {
 
 struct DistRow { double a, b, rho, m, sig; };
 
-__device__ __forceinline__ bool ds_pos(double v) { return v > 0.0 && v < __builtin_inf(); }          // finite and > 0
-__device__ __forceinline__ bool ds_fin(double v) { return __builtin_fabs(v) < __builtin_inf(); }     // finite
-
 // rule P1
 __device__ __forceinline__ bool ds_live(const DistRow& r, double S, double tau) {
-    if (!(ds_pos(S) && ds_pos(tau) && ds_fin(r.a) && ds_fin(r.b) && ds_fin(r.rho) && ds_fin(r.m) && ds_fin(r.sig))) return false;
+    if (!(finite_pos(S) && finite_pos(tau) && is_finite(r.a) && is_finite(r.b) && is_finite(r.rho) && is_finite(r.m) &&
+          is_finite(r.sig)))
+        return false;
     if (!(r.b >= 0.0 && __builtin_fabs(r.rho) <= 1.0 && r.sig > 0.0)) return false;
     return r.a + r.b * r.sig * sqrt(1.0 - r.rho * r.rho) > 0.0;
 }

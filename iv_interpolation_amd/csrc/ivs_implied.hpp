@@ -23,8 +23,6 @@ struct ImpliedParams {
     double* vol; int32_t* flags;
 };
 
-__device__ __forceinline__ bool iv_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }   // false for NaN
-
 // rule V6: the normalised out-of-the-money price at |log-moneyness| h and total vol s; em = exp(-h/2), ep = exp(h/2)
 __device__ __forceinline__ double iv_b(double h, double em, double ep, double s) {
     const double q = h / s, hs = 0.5 * s;
@@ -34,7 +32,7 @@ __device__ __forceinline__ double iv_b(double h, double em, double ep, double s)
 // rules V1, V8
 __device__ __forceinline__ void bs_price_one(double S, double K, double T, double r, double sg, bool put, double& price,
                                              double& vega, int32_t& flags) {
-    const bool live = iv_finite(S) && iv_finite(K) && iv_finite(T) && iv_finite(r) && iv_finite(sg) && S > 0.0 && K > 0.0 &&
+    const bool live = is_finite(S) && is_finite(K) && is_finite(T) && is_finite(r) && is_finite(sg) && S > 0.0 && K > 0.0 &&
                       T > 0.0 && sg > 0.0;
     const double sq = sqrt(T);
     const double KD = K * exp(-r * T);
@@ -50,7 +48,7 @@ __device__ __forceinline__ void bs_price_one(double S, double K, double T, doubl
 // rules V1-V7
 __device__ __forceinline__ void bs_implied_one(double price, double S, double K, double T, double r, bool put, int price_mode,
                                                double& vol, int32_t& flags) {
-    const bool live = iv_finite(price) && iv_finite(S) && iv_finite(K) && iv_finite(T) && iv_finite(r) && S > 0.0 && K > 0.0 &&
+    const bool live = is_finite(price) && is_finite(S) && is_finite(K) && is_finite(T) && is_finite(r) && S > 0.0 && K > 0.0 &&
                       T > 0.0 && price >= 0.0;
     const double P = price_mode ? price * S : price;                       // V2
     const double KD = K * exp(-r * T);                                     // V3

@@ -38,8 +38,6 @@ struct MomParams {
 struct MomSlot { double L, tau; int32_t flags, pad; };
 struct MomNode { double k, s, x, q; };                   // strike, vol, x = ln(k / F), q = Q / k^2
 
-__device__ __forceinline__ bool mm_pos(double v) { return v > 0.0 && v < __builtin_inf(); }   // finite and > 0
-
 __device__ __forceinline__ MomNode mm_from_lane(const MomNode& n, int src) {
     return MomNode{__shfl(n.k, src), __shfl(n.s, src), __shfl(n.x, src), __shfl(n.q, src)};
 }
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(MM_WAVES * 64) void surface_moments_kernel(MomParam
         const int64_t b = b0 + ls;
         const int64_t row = b * p.mT + j;
         const double S = p.spot[b], tau = p.Tq[b * p.tq_stride + j];
-        const bool live = mm_pos(S) && mm_pos(tau);                      // M1; uniform over the wavefront
+        const bool live = finite_pos(S) && finite_pos(tau);              // M1; uniform over the wavefront
         const double rt = p.rate * tau;
         const double F = S * exp(rt);                                    // M2
         double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(MM_WAVES * 64) void surface_moments_kernel(MomParam
                 const int i = c0 + lane;
                 const bool in = i < p.mK;
                 const double k = in ? kr[i] : qnan(), s = in ? vr[i] : qnan();
-                const bool valid = mm_pos(k) && mm_pos(s);
+                const bool valid = finite_pos(k) && finite_pos(s);
                 // M2, M3
                 const double x = log(k / S) - rt;
                 const double sq = sqrt(s * s * tau);

@@ -1,7 +1,9 @@
 // Book risk off the raw SVI slices (rules G0-G6, B1-B5): smile-aware Greeks per option and, over a book
 // of options, net Greeks and a scenario P&L grid per snapshot.  Both kernels read params [B][mT][5], the tenors, the spots and
-// Q options (u, tau, side) per snapshot, and place an option on the surface exactly as svi_eval_kernel does (rules T1-T3,
-// E1-E3 of section 14).
+// Q options (u, tau, side) per snapshot, and place an option on the surface as svi_eval_kernel does (rules T1-T3, E1-E3 of
+// section 14): the slices are staged by st_stage and the option is bracketed by st_bracket of ivs_svi_surface.hpp, the very
+// functions svi_eval_kernel calls.  The arithmetic on the bracket (rk_locate's weight, rk_w012, rk_surface) is this file's own
+// on account of rule B4 below.
 //
 // svi_greeks_kernel: the shape of svi_eval_kernel: a block takes one snapshot and 256 options, lane = option, the snapshot's
 // mT x 6 doubles staged in LDS once and read at uniform addresses.  An output left out is skipped with its arithmetic.
@@ -64,18 +66,6 @@ struct RkPoint {
     bool ok;
 };
 
-// rule T1 into LDS: a, b, rho, m, sigma, tau (NaN = dead) per tenor
-__device__ __forceinline__ void rk_stage(double* sl, const double* params, const double* Tq, int64_t tq_stride, int64_t b, int mT, double S) {
-    if ((int)threadIdx.x < mT) {
-        const int j = threadIdx.x;
-        const DistRow r = st_row(params + (b * mT + j) * 5);
-        const double tau = Tq[b * tq_stride + j];
-        const bool lv = ds_live(r, S, tau);
-        sl[j * 6 + 0] = r.a; sl[j * 6 + 1] = r.b; sl[j * 6 + 2] = r.rho; sl[j * 6 + 3] = r.m; sl[j * 6 + 4] = r.sig;
-        sl[j * 6 + 5] = lv ? tau : qnan();
-    }
-}
-
 // rule T3: w alone
 __device__ __forceinline__ double rk_w(const double* r, double x) {
 #pragma clang fp contract(off)
@@ -93,25 +83,14 @@ __device__ __forceinline__ void rk_w012(const double* r, double x, double& w, do
     w2 = r[1] * s2 / (rr * rr * rr);
 }
 
-// rules T2, E1, E2 and the weight of E3; `unordered` and `any` are the snapshot's
+// st_bracket's T2 and E2, then rule E1 and the weight of E3; `unordered` and `any` are the snapshot's
 __device__ __forceinline__ RkPoint rk_locate(const double* sl, int mT, double S, double u, double tq, double rate, int strike_mode,
                                              bool& unordered, bool& any) {
 #pragma clang fp contract(off)
     RkPoint pt;
-    int lo = -1, hi = -1;
-    unordered = false;
-    double prev = -__builtin_inf();
-    for (int j = 0; j < mT; ++j) {
-        const double t = sl[j * 6 + 5];
-        if (t == t) {
-            unordered = unordered || !(t > prev);
-            prev = t;
-        }
-        if (t <= tq) lo = j;
-        if (t > tq && hi < 0) hi = j;
-    }
-    any = prev > 0.0;
-    pt.ok = !unordered && ds_pos(u) && ds_pos(tq) && ds_pos(S) && any;
+    int lo, hi;
+    st_bracket(sl, mT, tq, lo, hi, unordered, any);
+    pt.ok = !unordered && finite_pos(u) && finite_pos(tq) && finite_pos(S) && any;
     pt.fl = unordered ? IVS_SE_UNORDERED : (pt.ok ? 0 : IVS_SE_DEAD);
     pt.K = pt.x = pt.rt = pt.D = pt.tl = pt.th_ = pt.lam = qnan();
     pt.lo = 0; pt.hi = -1;
@@ -214,7 +193,7 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_greeks_kernel(RiskParams p) {
     const int64_t b = blockIdx.x / p.nqb;
     const int qb = (int)(blockIdx.x - b * p.nqb);
     const double S = p.spot[b];
-    rk_stage(sl, p.params, p.Tq, p.tq_stride, b, p.mT, S);
+    st_stage(sl, p.params, p.Tq, p.tq_stride, b, p.mT, S);
     __syncthreads();
     const int64_t q = (int64_t)qb * RK_BLOCK + threadIdx.x;
     if (q >= p.Q) return;
@@ -262,7 +241,7 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_book_kernel(BookParams p) {
     const int nc = ncell - c0 < p.cpb ? ncell - c0 : p.cpb;              // <= RK_MAX_CELLS; 0 without a grid
     const bool first = ch == 0;                                          // this workgroup also owns net and n_dead
     const double S = p.spot[b];
-    rk_stage(sl, p.params, p.Tq, p.tq_stride, b, p.mT, S);
+    st_stage(sl, p.params, p.Tq, p.tq_stride, b, p.mT, S);
     __syncthreads();
 
     double tot_ss = 0.0, tot_sm = 0.0, ntot = 0.0;                       // thread t: cell c0 + t; thread k < 8: net figure k

@@ -29,8 +29,6 @@ struct SmileParams {
     double* q_vol; double* q_strike; int32_t* q_flags;   // [rows][nD]
 };
 
-__device__ __forceinline__ bool sm_pos(double v) { return v > 0.0 && v < __builtin_inf(); }   // finite and > 0
-
 // rule D1: bs_greeks_one's d1, spelled the same way (sq = sqrt(tau))
 __device__ __forceinline__ double sm_d1(double S, double k, double s, double r, double tau, double sq) {
     return (log(S / k) + (r + 0.5 * s * s) * tau) / (s * sq);
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(SM_WAVES * 64) void smile_delta_kernel(SmileParams 
         const int j = (int)(row - b * p.mT);
         const double S = p.spot[b], tau = p.Tq[b * p.tq_stride + j];
         int nvalid = 0;
-        if (sm_pos(S) && sm_pos(tau)) {                                  // D2; uniform over the wavefront
+        if (finite_pos(S) && finite_pos(tau)) {                          // D2; uniform over the wavefront
             const double sq = sqrt(tau);
             const double* kr = p.Kq + b * p.kq_stride;
             const double* vr = p.vol + row * p.mK;
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(SM_WAVES * 64) void smile_delta_kernel(SmileParams 
                 const int64_t i = c0 + lane;
                 const bool in = i < p.mK;
                 const double k = in ? kr[i] : qnan(), s = in ? vr[i] : qnan();
-                const bool valid = sm_pos(k) && sm_pos(s);
+                const bool valid = finite_pos(k) && finite_pos(s);
                 const double d1 = sm_d1(S, k, s, p.rate, tau, sq);
                 const unsigned long long vm = __ballot(valid);
                 const unsigned long long below = vm & ((1ull << lane) - 1ull);

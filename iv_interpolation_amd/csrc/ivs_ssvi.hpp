@@ -90,7 +90,7 @@ __global__ __launch_bounds__(SS_THREADS) void ssvi_surface_kernel(SsviParams p) 
             const DistRow r = st_row(p.raw + row * 5);
             th0 = ds_live(r, S, tau) ? ss_w0(r) : qnan();
         }
-        const bool live = ds_pos(S) && ds_pos(tau) && ds_pos(th0);
+        const bool live = finite_pos(S) && finite_pos(tau) && finite_pos(th0);
         int n = 0, ifirst = -1, ilast = -1;
         if (live) {
             const double* vr = p.vol + row * mK;
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(SS_THREADS) void ssvi_surface_kernel(SsviParams p) 
                 const int i = c0 + lane;
                 const bool in = i < mK;
                 const double k = in ? kr[i] : qnan(), s = in ? vr[i] : qnan();
-                const unsigned long long vm = __ballot(ds_pos(k) && ds_pos(s));
+                const unsigned long long vm = __ballot(finite_pos(k) && finite_pos(s));
                 if (vm) {
                     if (n == 0) ifirst = c0 + __builtin_ctzll(vm);
                     ilast = c0 + 63 - __builtin_clzll(vm);
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(SS_THREADS) void ssvi_surface_kernel(SsviParams p) 
                 const int i = c0 + lane;
                 const bool in = i < mK;
                 const double k = in ? kr[i] : qnan(), s = in ? vr[i] : qnan();
-                const bool valid = ds_pos(k) && ds_pos(s);
+                const bool valid = finite_pos(k) && finite_pos(s);
                 const unsigned long long vm = __ballot(valid);
                 if (valid) {
                     const int at = n + __popcll(vm & ((1ull << lane) - 1ull));   // at < l_off[l + 1] <= mT * mK
@@ -262,14 +262,14 @@ __global__ __launch_bounds__(SS_THREADS) void ssvi_surface_kernel(SsviParams p) 
             const int i = c0 + lane;
             if (i >= mK) continue;
             const double k = kr[i], s = vr[i];
-            const bool kpos = ds_pos(k);
+            const bool kpos = finite_pos(k);
             const double x = log(k / S) - rt;
             const double px = phi * x;
             const double t = px + rho;
             const double wf = 0.5 * th * (1.0 + rho * px + sqrt(t * t + omr));
             const double vf = sqrt((wf > 0.0 ? wf : 0.0) / tau);
             if (fr) fr[i] = kpos ? vf : qnan();
-            if (kpos && ds_pos(s)) {
+            if (kpos && finite_pos(s)) {
                 const double e = vf - s;
                 se2 += e * e;
                 emax = __builtin_fabs(e) > emax ? __builtin_fabs(e) : emax;

@@ -33,8 +33,6 @@ struct SviParams {
     double* params; double* fit; int32_t* flags; double* fitted;   // [rows][5], [rows][4], [rows], [rows][mK] or null
 };
 
-__device__ __forceinline__ bool sv_pos(double v) { return v > 0.0 && v < __builtin_inf(); }   // finite and > 0
-
 // V4: set s = 9 ia + icd; the states of p = (c - d) / 2 and q = (c + d) / 2 (0 free, 1 at 0, 2 at sigma) of icd = interior,
 // d = c, d = -c, c + d = 2 sigma, c - d = 2 sigma, (0, 0), (sigma, sigma), (2 sigma, 0), (sigma, -sigma), two bits each
 constexpr uint32_t SV_P_STATES = 0u | 1u << 2 | 0u << 4 | 0u << 6 | 2u << 8 | 1u << 10 | 1u << 12 | 2u << 14 | 2u << 16;
@@ -118,7 +116,7 @@ __global__ __launch_bounds__(SV_WAVES * 64) void svi_slice_kernel(SviParams p) {
     const int64_t b = mine ? row / p.mT : 0;
     const int j = mine ? (int)(row - b * p.mT) : 0;
     const double S = mine ? p.spot[b] : qnan(), tau = mine ? p.Tq[b * p.tq_stride + j] : qnan();
-    const bool live = mine && sv_pos(S) && sv_pos(tau);                  // V1
+    const bool live = mine && finite_pos(S) && finite_pos(tau);          // V1
     const double rt = p.rate * tau;
     const double* kr = p.Kq + b * p.kq_stride;
     const double* vr = p.vol + (mine ? row : 0) * p.mK;
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(SV_WAVES * 64) void svi_slice_kernel(SviParams p) {
             const int i = c0 + lane;
             const bool in = i < p.mK;
             const double k = in ? kr[i] : qnan(), s = in ? vr[i] : qnan();
-            const bool valid = sv_pos(k) && sv_pos(s);
+            const bool valid = finite_pos(k) && finite_pos(s);
             const unsigned long long vm = __ballot(valid);
             const unsigned long long above = vm & ~((2ull << lane) - 1ull);
             const double knext = __shfl(k, above ? __builtin_ctzll(above) : lane);
@@ -217,14 +215,14 @@ __global__ __launch_bounds__(SV_WAVES * 64) void svi_slice_kernel(SviParams p) {
                 continue;
             }
             const double k = kr[i], s = vr[i];
-            const bool kpos = sv_pos(k);
+            const bool kpos = finite_pos(k);
             const double x = log(k / S) - rt;
             const double dx = x - rm;
             const double r = sqrt(dx * dx + rsig * rsig);
             const double wf = ra + pb * (prho * dx + r);
             const double vf = sqrt((wf > 0.0 ? wf : 0.0) / tau);
             if (fr) fr[i] = kpos ? vf : qnan();
-            if (kpos && sv_pos(s)) {
+            if (kpos && finite_pos(s)) {
                 const double e = vf - s;
                 se2 += e * e;
                 emax = __builtin_fabs(e) > emax ? __builtin_fabs(e) : emax;

@@ -85,6 +85,43 @@ __device__ __forceinline__ double sc_s0(const DistRow& lo, const DistRow& hi) {
 
 __device__ __forceinline__ DistRow st_row(const double* pr) { return DistRow{pr[0], pr[1], pr[2], pr[3], pr[4]}; }
 
+// Where a (strike, expiry) sits between the slices of snapshot b.  svi_eval_kernel and the two kernels of ivs_risk.hpp place
+// a query through these two functions, so they cannot disagree.
+//
+// rule T1 into LDS: a, b, rho, m, sigma, tau (NaN = dead, so that no comparison ever picks it) per tenor; the caller
+// synchronises the block before it reads sl
+__device__ __forceinline__ void st_stage(double* sl, const double* params, const double* Tq, int64_t tq_stride, int64_t b, int mT, double S) {
+    if ((int)threadIdx.x < mT) {
+        const int j = threadIdx.x;
+        const DistRow r = st_row(params + (b * mT + j) * 5);
+        const double tau = Tq[b * tq_stride + j];
+        const bool lv = ds_live(r, S, tau);
+        sl[j * 6 + 0] = r.a; sl[j * 6 + 1] = r.b; sl[j * 6 + 2] = r.rho; sl[j * 6 + 3] = r.m; sl[j * 6 + 4] = r.sig;
+        sl[j * 6 + 5] = lv ? tau : qnan();
+    }
+}
+
+// rules T2 and E2 on the staged slices: lo = the last live slice with tenor <= tq, hi = the first with tenor > tq (-1 = none);
+// unordered = the live tenors do not strictly increase; any = there is a live slice.  A fixed loop at uniform LDS addresses,
+// comparisons only: no floating-point setting can change what it yields.  The loop runs on locals and the four results are
+// handed over once, after it: written through the references inside the loop, the same code made svi_eval_kernel about 1 %
+// slower on MI355X (profiles/analytics_refactor/bench.txt).
+__device__ __forceinline__ void st_bracket(const double* sl, int mT, double tq, int& lo_, int& hi_, bool& unordered_, bool& any_) {
+    int lo = -1, hi = -1;
+    bool unordered = false;
+    double prev = -__builtin_inf();
+    for (int j = 0; j < mT; ++j) {
+        const double t = sl[j * 6 + 5];
+        if (t == t) {
+            unordered = unordered || !(t > prev);
+            prev = t;
+        }
+        if (t <= tq) lo = j;
+        if (t > tq && hi < 0) hi = j;
+    }
+    lo_ = lo; hi_ = hi; unordered_ = unordered; any_ = prev > 0.0;
+}
+
 __global__ __launch_bounds__(SC_WAVES * 64) void svi_calendar_kernel(CalParams p) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -196,34 +233,16 @@ __global__ __launch_bounds__(SE_BLOCK) void svi_eval_kernel(EvalParams p) {
     const int64_t b = blockIdx.x / p.nqb;
     const int qb = (int)(blockIdx.x - b * p.nqb);
     const double S = p.spot[b];
-    if ((int)threadIdx.x < p.mT) {                                       // T1
-        const int j = threadIdx.x;
-        const double* pr = p.params + (b * p.mT + j) * 5;
-        const DistRow r = st_row(pr);
-        const double tau = p.Tq[b * p.tq_stride + j];
-        const bool lv = ds_live(r, S, tau);
-        sl[j * 6 + 0] = r.a; sl[j * 6 + 1] = r.b; sl[j * 6 + 2] = r.rho; sl[j * 6 + 3] = r.m; sl[j * 6 + 4] = r.sig;
-        sl[j * 6 + 5] = lv ? tau : qnan();
-    }
+    st_stage(sl, p.params, p.Tq, p.tq_stride, b, p.mT, S);               // T1
     __syncthreads();
     const int64_t q = (int64_t)qb * SE_BLOCK + threadIdx.x;
     if (q >= p.Q) return;
     const double u = p.u[b * p.q_stride + q], tq = p.tau[b * p.q_stride + q];
 
-    int lo = -1, hi = -1;                                                // E2 and T2: a fixed loop, uniform LDS addresses
-    bool unordered = false;
-    double prev = -__builtin_inf();
-    for (int j = 0; j < p.mT; ++j) {
-        const double t = sl[j * 6 + 5];
-        if (t == t) {
-            unordered = unordered || !(t > prev);
-            prev = t;
-        }
-        if (t <= tq) lo = j;
-        if (t > tq && hi < 0) hi = j;
-    }
-    const bool any = prev > 0.0;
-    const bool ok = ds_pos(u) && ds_pos(tq) && ds_pos(S) && any;         // E1
+    int lo, hi;
+    bool unordered, any;
+    st_bracket(sl, p.mT, tq, lo, hi, unordered, any);                    // T2 and E2
+    const bool ok = finite_pos(u) && finite_pos(tq) && finite_pos(S) && any;  // E1
 
     int32_t fl = 0;
     double W = qnan(), vol = qnan(), call = qnan(), put = qnan(), V = qnan(), g = qnan(), lv = qnan();

@@ -48,6 +48,105 @@ def _hold_for_stream(torch, stream, *tensors):
             t.record_stream(stream)
 
 
+# ---- the host checks and call steps the snapshot-analytics wrappers share
+
+def _tenor_inputs(Tq, spot, B, mT):
+    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
+        raise ValueError("Tq must be [mT] or [B, mT]")
+    if spot.numel() != B:
+        raise ValueError("spot must hold one price per surface")
+
+
+def _surface_inputs(torch, vol, Kq, Tq, spot):
+    """The shared input checks of the stages that read surfaces: vol [B,mT,mK], Kq [mK] or [B,mK], Tq [mT] or [B,mT], spot [B]."""
+    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if vol.dim() != 3:
+        raise ValueError("vol must be [B, mT, mK]")
+    B, mT, mK = vol.shape
+    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
+        raise ValueError("Kq must be [mK] or [B, mK]")
+    _tenor_inputs(Tq, spot, B, mT)
+    return vol, Kq, Tq, spot, B, mT, mK
+
+
+def _svi_inputs(torch, params, Tq, spot, max_tenors=_lib.ST_MAX_TENORS):
+    """The shared input checks of the stages that read SVI slices: params [B,mT,5], Tq [mT] or [B,mT], spot [B], and at most
+    max_tenors slices per snapshot (None: no limit)."""
+    params = _f64(torch, params, "params"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
+    if params.dim() != 3 or params.shape[-1] != 5:
+        raise ValueError("params must be [B, mT, 5]")
+    B, mT, _ = params.shape
+    _tenor_inputs(Tq, spot, B, mT)
+    if max_tenors is not None and mT > max_tenors:
+        raise ValueError(f"mT = {mT}: at most {max_tenors} tenors per snapshot are supported")
+    return params, Tq, spot, B, mT
+
+
+def _surface_fields(a, vol, Kq, Tq, spot, rate):
+    """The fields every args struct of a surface stage has: the surfaces, their two grids, the spots and the rate."""
+    B, mT, mK = vol.shape
+    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
+    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
+    a.mK, a.mT, a.B = mK, mT, B
+    return a
+
+
+def _slice_fields(a, params, Tq, spot, rate=None):
+    """The fields every args struct of a stage on SVI slices has (the calendar has no rate)."""
+    B, mT, _ = params.shape
+    a.params, a.Tq, a.tq_stride, a.spot = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot)
+    a.mT, a.B = mT, B
+    if rate is not None:
+        a.rate = float(rate)
+    return a
+
+
+def _query_fields(a, u, tau, strike_mode):
+    Q = u.shape[-1]
+    a.u, a.tau, a.q_stride, a.strike_mode, a.Q = _ptr(u), _ptr(tau), (0 if u.dim() == 1 else Q), int(strike_mode), Q
+
+
+def _doubles(xs):
+    """A short host list as the const double* of an args struct (one slot even when empty).  The pointer keeps its array
+    alive, and the struct the pointer."""
+    import ctypes
+    return ctypes.cast((ctypes.c_double * max(len(xs), 1))(*xs), ctypes.POINTER(ctypes.c_double))
+
+
+def _wanted(want, names):
+    want = tuple(want)
+    if any(k not in names for k in want):
+        raise ValueError(f"want must name outputs among {names}, got {want!r}")
+    return want
+
+
+def _outputs(torch, out, shapes, device, per_option=False):
+    """`out` (a dict of preallocated tensors, or None) completed to every key of shapes = {key: (shape, dtype, wanted)}: a
+    tensor given is checked, one missing is allocated, one not wanted is None.  per_option: the flat pricers take a tensor
+    given in any shape with as many elements."""
+    import math
+    out = dict(out or {})
+    for k, (shape, dt, on) in shapes.items():
+        t = out.get(k)
+        if not on:
+            out[k] = None
+        elif t is None:
+            out[k] = torch.empty(shape, dtype=dt, device=device)
+        else:
+            bad_shape = t.numel() != math.prod(shape) if per_option else tuple(t.shape) != shape
+            if bad_shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                what = "with one entry per option" if per_option else f"of shape {shape}"
+                raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor {what}")
+    return out
+
+
+def _call(torch, name, a, stream, *tensors):
+    """Run the C entry point `name` on the args struct, keep `tensors` alive for `stream`, raise EngineError on failure."""
+    rc = getattr(_lib.load(), name)(a, None, 0, _stream(torch, stream))
+    _hold_for_stream(torch, stream, *tensors)
+    _lib.check(rc, name)
+
+
 def validate_ragged(K, sigma, k_off, nK_max: int, n_maturities: int):
     """Optional host-side check of CSR offsets with a readable exception (one small device reduction + one D2H read, i.e. it
     SYNCHRONISES: not for capture).  The kernels do not depend on it: they check every span against nK_max and against the
@@ -149,7 +248,6 @@ def snapshot_assemble(date_ns, iv, underlying, row_off, cells, strike, expiry_ns
     `out`: optional dict of preallocated outputs (keys sigma [B,nT,nK], T [B,nT], spot [B], quotes int32 [B], Kq [B,mK]).
     Returns dict(sigma, T, spot, quotes, Kq) of device tensors (Kq None without moneyness)."""
     torch = require_device()
-    lib = _lib.load()
     iv = _f64(torch, iv, "iv"); underlying = _f64(torch, underlying, "underlying"); strike = _f64(torch, strike, "strike")
     for t, name, dt in ((date_ns, "date_ns", torch.int64), (row_off, "row_off", torch.int64), (cells, "cells", torch.int32),
                         (expiry_ns, "expiry_ns", torch.int64)):
@@ -165,19 +263,10 @@ def snapshot_assemble(date_ns, iv, underlying, row_off, cells, strike, expiry_ns
     if moneyness is not None:
         moneyness = _f64(torch, moneyness, "moneyness")
     mK = 0 if moneyness is None else moneyness.numel()
-    dev = iv.device
-    out = dict(out or {})
-    shapes = {"sigma": ((B, nT, nK), torch.float64), "T": ((B, nT), torch.float64), "spot": ((B,), torch.float64),
-              "quotes": ((B,), torch.int32), "Kq": ((B, mK), torch.float64)}
-    for k, (shape, dt) in shapes.items():
-        if k == "Kq" and moneyness is None:
-            out[k] = None
-            continue
-        t = out.get(k)
-        if t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=dev)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
+    shapes = {"sigma": ((B, nT, nK), torch.float64, True), "T": ((B, nT), torch.float64, True),
+              "spot": ((B,), torch.float64, True), "quotes": ((B,), torch.int32, True),
+              "Kq": ((B, mK), torch.float64, moneyness is not None)}
+    out = _outputs(torch, out, shapes, iv.device)
     a = _lib.SnapshotArgs()
     a.date_ns, a.iv, a.underlying, a.n_rows = _ptr(date_ns), _ptr(iv), _ptr(underlying), n
     a.row_off, a.n_contracts = _ptr(row_off), row_off.numel() - 1
@@ -185,9 +274,8 @@ def snapshot_assemble(date_ns, iv, underlying, row_off, cells, strike, expiry_ns
     a.t0_ns, a.n_snapshots = int(t0_ns), B
     a.moneyness, a.mK, a.kq_empty = _ptr(moneyness), mK, float(kq_empty)
     a.sigma, a.T, a.spot, a.quotes, a.Kq = (_ptr(out[k]) for k in ("sigma", "T", "spot", "quotes", "Kq"))
-    rc = lib.ivs_snapshot_assemble_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, date_ns, iv, underlying, row_off, cells, strike, expiry_ns, moneyness, *out.values())
-    _lib.check(rc, "ivs_snapshot_assemble_f64")
+    _call(torch, "ivs_snapshot_assemble_f64", a, stream, date_ns, iv, underlying, row_off, cells, strike, expiry_ns, moneyness,
+          *out.values())
     return out
 
 
@@ -222,39 +310,18 @@ def smile_delta_points(vol, Kq, Tq, spot, deltas=DEFAULT_DELTAS, rate: float = 0
     rows_per_wave: 0 lets the call choose how many rows share a wavefront; 1..64 // nD forces it (tuning / testing; the
     results are the same bit for bit).
     Returns dict(vol, strike, flags) of device tensors; flags are the _lib.SM_* bits."""
-    import ctypes
     z = delta_targets(deltas)
     torch = require_device()
-    lib = _lib.load()
-    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
-    if vol.dim() != 3:
-        raise ValueError("vol must be [B, mT, mK]")
-    B, mT, mK = vol.shape
-    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
-        raise ValueError("Kq must be [mK] or [B, mK]")
-    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
-        raise ValueError("Tq must be [mT] or [B, mT]")
-    if spot.numel() != B:
-        raise ValueError("spot must hold one price per surface")
+    vol, Kq, Tq, spot, B, mT, mK = _surface_inputs(torch, vol, Kq, Tq, spot)
     nD = len(z)
-    out = dict(out or {})
-    for k, dt in (("vol", torch.float64), ("strike", torch.float64), ("flags", torch.int32)):
-        t = out.get(k)
-        if t is None:
-            out[k] = torch.empty((B, mT, nD), dtype=dt, device=vol.device)
-        elif tuple(t.shape) != (B, mT, nD) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {(B, mT, nD)}")
-    zbuf = (ctypes.c_double * nD)(*z)
-    a = _lib.SmileArgs()
-    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
-    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
-    a.z = ctypes.cast(zbuf, ctypes.POINTER(ctypes.c_double))
-    a.mK, a.mT, a.nD, a.B = mK, mT, nD, B
+    shapes = {"vol": ((B, mT, nD), torch.float64, True), "strike": ((B, mT, nD), torch.float64, True),
+              "flags": ((B, mT, nD), torch.int32, True)}
+    out = _outputs(torch, out, shapes, vol.device)
+    a = _surface_fields(_lib.SmileArgs(), vol, Kq, Tq, spot, rate)
+    a.z, a.nD = _doubles(z), nD
     a.q_vol, a.q_strike, a.q_flags = _ptr(out["vol"]), _ptr(out["strike"]), _ptr(out["flags"])
     a.rows_per_wave = int(rows_per_wave)
-    rc = lib.ivs_smile_delta_points_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
-    _lib.check(rc, "ivs_smile_delta_points_f64")
+    _call(torch, "ivs_smile_delta_points_f64", a, stream, vol, Kq, Tq, spot, *out.values())
     return out
 
 
@@ -269,39 +336,16 @@ def surface_arbitrage(vol, Kq, Tq, spot, rate: float = 0.0, *, local_vol: bool =
     Returns dict(flags, counts, worst, local_vol, density) of device tensors (None for a field left out); flags are the
     _lib.AR_* bits, counts = evaluated, calendar, butterfly, finite local-vol nodes, worst = min numerator, min g."""
     torch = require_device()
-    lib = _lib.load()
-    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
-    if vol.dim() != 3:
-        raise ValueError("vol must be [B, mT, mK]")
-    B, mT, mK = vol.shape
-    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
-        raise ValueError("Kq must be [mK] or [B, mK]")
-    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
-        raise ValueError("Tq must be [mT] or [B, mT]")
-    if spot.numel() != B:
-        raise ValueError("spot must hold one price per surface")
-    out = dict(out or {})
-    want = {"flags": ((B, mT, mK), torch.int32, True), "counts": ((B, 4), torch.int32, True),
-            "worst": ((B, 2), torch.float64, True), "local_vol": ((B, mT, mK), torch.float64, bool(local_vol)),
-            "density": ((B, mT, mK), torch.float64, bool(density))}
-    for k, (shape, dt, on) in want.items():
-        t = out.get(k)
-        if not on:
-            out[k] = None
-        elif t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    a = _lib.ArbitrageArgs()
-    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
-    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
-    a.mK, a.mT, a.B = mK, mT, B
+    vol, Kq, Tq, spot, B, mT, mK = _surface_inputs(torch, vol, Kq, Tq, spot)
+    shapes = {"flags": ((B, mT, mK), torch.int32, True), "counts": ((B, 4), torch.int32, True),
+              "worst": ((B, 2), torch.float64, True), "local_vol": ((B, mT, mK), torch.float64, bool(local_vol)),
+              "density": ((B, mT, mK), torch.float64, bool(density))}
+    out = _outputs(torch, out, shapes, vol.device)
+    a = _surface_fields(_lib.ArbitrageArgs(), vol, Kq, Tq, spot, rate)
     a.flags, a.counts, a.worst = _ptr(out["flags"]), _ptr(out["counts"]), _ptr(out["worst"])
     a.local_vol, a.density = _ptr(out["local_vol"]), _ptr(out["density"])
-    rc = lib.ivs_surface_arbitrage_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
-    _lib.check(rc, "ivs_surface_arbitrage_f64")
-    return {k: out[k] for k in want}
+    _call(torch, "ivs_surface_arbitrage_f64", a, stream, vol, Kq, Tq, spot, *out.values())
+    return {k: out[k] for k in shapes}
 
 
 def surface_moments(vol, Kq, Tq, spot, rate: float = 0.0, *, horizons=(30.0 / 365.0,), min_mass: float = 0.99, out=None,
@@ -317,7 +361,6 @@ def surface_moments(vol, Kq, Tq, spot, rate: float = 0.0, *, horizons=(30.0 / 36
     results are the same bit for bit).
     Returns dict(raw, stats, mass, flags, index, index_flags) of device tensors (index / index_flags None without
     horizons); raw = L, V, W, X; stats = mf_vol, bkm_vol, skew, kurt; flags are the _lib.MM_* bits."""
-    import ctypes
     import math
     hz = [float(h) for h in horizons]
     if len(hz) > _lib.MM_MAX_HORIZONS:
@@ -327,43 +370,20 @@ def surface_moments(vol, Kq, Tq, spot, rate: float = 0.0, *, horizons=(30.0 / 36
     if not 0.0 <= float(min_mass) <= 1.0:
         raise ValueError(f"min_mass {min_mass!r} is outside [0, 1]")
     torch = require_device()
-    lib = _lib.load()
-    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
-    if vol.dim() != 3:
-        raise ValueError("vol must be [B, mT, mK]")
-    B, mT, mK = vol.shape
-    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
-        raise ValueError("Kq must be [mK] or [B, mK]")
-    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
-        raise ValueError("Tq must be [mT] or [B, mT]")
-    if spot.numel() != B:
-        raise ValueError("spot must hold one price per surface")
+    vol, Kq, Tq, spot, B, mT, mK = _surface_inputs(torch, vol, Kq, Tq, spot)
     nH = len(hz)
-    out = dict(out or {})
-    want = {"raw": ((B, mT, 4), torch.float64, True), "stats": ((B, mT, 4), torch.float64, True),
-            "mass": ((B, mT), torch.float64, True), "flags": ((B, mT), torch.int32, True),
-            "index": ((B, nH), torch.float64, nH > 0), "index_flags": ((B, nH), torch.int32, nH > 0)}
-    for k, (shape, dt, on) in want.items():
-        t = out.get(k)
-        if not on:
-            out[k] = None
-        elif t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    hbuf = (ctypes.c_double * max(nH, 1))(*hz)
-    a = _lib.MomentsArgs()
-    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
-    a.Tq, a.tq_stride, a.spot, a.rate, a.min_mass = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate), float(min_mass)
-    a.horizons, a.nH = ctypes.cast(hbuf, ctypes.POINTER(ctypes.c_double)), nH
-    a.mK, a.mT, a.B = mK, mT, B
+    shapes = {"raw": ((B, mT, 4), torch.float64, True), "stats": ((B, mT, 4), torch.float64, True),
+              "mass": ((B, mT), torch.float64, True), "flags": ((B, mT), torch.int32, True),
+              "index": ((B, nH), torch.float64, nH > 0), "index_flags": ((B, nH), torch.int32, nH > 0)}
+    out = _outputs(torch, out, shapes, vol.device)
+    a = _surface_fields(_lib.MomentsArgs(), vol, Kq, Tq, spot, rate)
+    a.min_mass = float(min_mass)
+    a.horizons, a.nH = _doubles(hz), nH
     a.raw, a.stats, a.mass, a.flags = _ptr(out["raw"]), _ptr(out["stats"]), _ptr(out["mass"]), _ptr(out["flags"])
     a.index, a.index_flags = _ptr(out["index"]), _ptr(out["index_flags"])
     a.snapshots_per_wg = int(snapshots_per_wg)
-    rc = lib.ivs_surface_moments_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
-    _lib.check(rc, "ivs_surface_moments_f64")
-    return {k: out[k] for k in want}
+    _call(torch, "ivs_surface_moments_f64", a, stream, vol, Kq, Tq, spot, *out.values())
+    return {k: out[k] for k in shapes}
 
 
 def svi_slices(vol, Kq, Tq, spot, rate: float = 0.0, *, rounds: int = 0, fitted: bool = False, out=None, stream=None,
@@ -383,38 +403,16 @@ def svi_slices(vol, Kq, Tq, spot, rate: float = 0.0, *, rounds: int = 0, fitted:
     if not 0 <= int(rounds) <= _lib.SV_MAX_ROUNDS:
         raise ValueError(f"rounds {rounds!r} is outside [0, {_lib.SV_MAX_ROUNDS}]")
     torch = require_device()
-    lib = _lib.load()
-    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
-    if vol.dim() != 3:
-        raise ValueError("vol must be [B, mT, mK]")
-    B, mT, mK = vol.shape
-    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
-        raise ValueError("Kq must be [mK] or [B, mK]")
-    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
-        raise ValueError("Tq must be [mT] or [B, mT]")
-    if spot.numel() != B:
-        raise ValueError("spot must hold one price per surface")
-    out = dict(out or {})
-    want = {"params": ((B, mT, 5), torch.float64, True), "fit": ((B, mT, 4), torch.float64, True),
-            "flags": ((B, mT), torch.int32, True), "fitted": ((B, mT, mK), torch.float64, bool(fitted))}
-    for k, (shape, dt, on) in want.items():
-        t = out.get(k)
-        if not on:
-            out[k] = None
-        elif t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    a = _lib.SviArgs()
-    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
-    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
-    a.mK, a.mT, a.B, a.rounds = mK, mT, B, int(rounds)
+    vol, Kq, Tq, spot, B, mT, mK = _surface_inputs(torch, vol, Kq, Tq, spot)
+    shapes = {"params": ((B, mT, 5), torch.float64, True), "fit": ((B, mT, 4), torch.float64, True),
+              "flags": ((B, mT), torch.int32, True), "fitted": ((B, mT, mK), torch.float64, bool(fitted))}
+    out = _outputs(torch, out, shapes, vol.device)
+    a = _surface_fields(_lib.SviArgs(), vol, Kq, Tq, spot, rate)
+    a.rounds = int(rounds)
     a.params, a.fit, a.flags, a.fitted = _ptr(out["params"]), _ptr(out["fit"]), _ptr(out["flags"]), _ptr(out["fitted"])
     a.rows_per_wg = int(rows_per_wg)
-    rc = lib.ivs_svi_slices_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, *out.values())
-    _lib.check(rc, "ivs_svi_slices_f64")
-    return {k: out[k] for k in want}
+    _call(torch, "ivs_svi_slices_f64", a, stream, vol, Kq, Tq, spot, *out.values())
+    return {k: out[k] for k in shapes}
 
 
 def ssvi_surface(vol, Kq, Tq, spot, rate: float = 0.0, *, raw=None, theta0=None, rounds: int = 0, fitted: bool = False,
@@ -437,17 +435,7 @@ def ssvi_surface(vol, Kq, Tq, spot, rate: float = 0.0, *, raw=None, theta0=None,
     if (raw is None) == (theta0 is None):
         raise ValueError("exactly one of raw and theta0 must be given")
     torch = require_device()
-    lib = _lib.load()
-    vol = _f64(torch, vol, "vol"); Kq = _f64(torch, Kq, "Kq"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
-    if vol.dim() != 3:
-        raise ValueError("vol must be [B, mT, mK]")
-    B, mT, mK = vol.shape
-    if Kq.dim() not in (1, 2) or Kq.shape[-1] != mK or (Kq.dim() == 2 and Kq.shape[0] != B):
-        raise ValueError("Kq must be [mK] or [B, mK]")
-    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
-        raise ValueError("Tq must be [mT] or [B, mT]")
-    if spot.numel() != B:
-        raise ValueError("spot must hold one price per surface")
+    vol, Kq, Tq, spot, B, mT, mK = _surface_inputs(torch, vol, Kq, Tq, spot)
     if mT > _lib.ST_MAX_TENORS:
         raise ValueError(f"mT = {mT}: at most {_lib.ST_MAX_TENORS} tenors per snapshot are supported")
     if mK < 1 or mT * mK > _lib.SS_MAX_NODES:
@@ -460,30 +448,17 @@ def ssvi_surface(vol, Kq, Tq, spot, rate: float = 0.0, *, raw=None, theta0=None,
         theta0 = _f64(torch, theta0, "theta0")
         if tuple(theta0.shape) != (B, mT):
             raise ValueError("theta0 must be [B, mT]")
-    out = dict(out or {})
-    want = {"surface": ((B, 4), torch.float64, True), "theta": ((B, mT), torch.float64, True),
-            "params": ((B, mT, 5), torch.float64, True), "fit": ((B, mT, 3), torch.float64, True),
-            "flags": ((B, mT), torch.int32, True), "sflags": ((B,), torch.int32, True),
-            "fitted": ((B, mT, mK), torch.float64, bool(fitted))}
-    for k, (shape, dt, on) in want.items():
-        t = out.get(k)
-        if not on:
-            out[k] = None
-        elif t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=vol.device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    a = _lib.SsviArgs()
-    a.vol, a.Kq, a.kq_stride = _ptr(vol), _ptr(Kq), (0 if Kq.dim() == 1 else mK)
-    a.Tq, a.tq_stride, a.spot, a.rate = _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
-    a.raw, a.theta0 = _ptr(raw), _ptr(theta0)
-    a.mK, a.mT, a.B, a.rounds = mK, mT, B, int(rounds)
+    shapes = {"surface": ((B, 4), torch.float64, True), "theta": ((B, mT), torch.float64, True),
+              "params": ((B, mT, 5), torch.float64, True), "fit": ((B, mT, 3), torch.float64, True),
+              "flags": ((B, mT), torch.int32, True), "sflags": ((B,), torch.int32, True),
+              "fitted": ((B, mT, mK), torch.float64, bool(fitted))}
+    out = _outputs(torch, out, shapes, vol.device)
+    a = _surface_fields(_lib.SsviArgs(), vol, Kq, Tq, spot, rate)
+    a.raw, a.theta0, a.rounds = _ptr(raw), _ptr(theta0), int(rounds)
     a.surface, a.theta, a.params, a.fit = _ptr(out["surface"]), _ptr(out["theta"]), _ptr(out["params"]), _ptr(out["fit"])
     a.flags, a.sflags, a.fitted = _ptr(out["flags"]), _ptr(out["sflags"]), _ptr(out["fitted"])
-    rc = lib.ivs_ssvi_surface_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, vol, Kq, Tq, spot, raw, theta0, *out.values())
-    _lib.check(rc, "ivs_ssvi_surface_f64")
-    return {k: out[k] for k in want}
+    _call(torch, "ivs_ssvi_surface_f64", a, stream, vol, Kq, Tq, spot, raw, theta0, *out.values())
+    return {k: out[k] for k in shapes}
 
 
 DEFAULT_PROBS = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)      # rule P9: the probability cone
@@ -521,61 +496,24 @@ def svi_distribution(params, Tq, spot, rate: float = 0.0, *, probs=DEFAULT_PROBS
     results are the same bit for bit).
     Returns dict(q_x, q_strike, q_flags, p_below, p_above, tails, flags) of device tensors (p_below / p_above None without
     levels); the flags are the _lib.DS_* bits."""
-    import ctypes
     probs, levels = distribution_targets(probs, levels, max_tail)
     torch = require_device()
-    lib = _lib.load()
-    params = _f64(torch, params, "params"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
-    if params.dim() != 3 or params.shape[-1] != 5:
-        raise ValueError("params must be [B, mT, 5]")
-    B, mT, _ = params.shape
-    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
-        raise ValueError("Tq must be [mT] or [B, mT]")
-    if spot.numel() != B:
-        raise ValueError("spot must hold one price per surface")
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot, max_tenors=None)     # the rows are independent: any mT
     nP, nL = len(probs), len(levels)
-    out = dict(out or {})
-    want = {"q_x": ((B, mT, nP), torch.float64, True), "q_strike": ((B, mT, nP), torch.float64, True),
-            "q_flags": ((B, mT, nP), torch.int32, True), "p_below": ((B, mT, nL), torch.float64, nL > 0),
-            "p_above": ((B, mT, nL), torch.float64, nL > 0), "tails": ((B, mT, 2), torch.float64, True),
-            "flags": ((B, mT), torch.int32, True)}
-    for k, (shape, dt, on) in want.items():
-        t = out.get(k)
-        if not on:
-            out[k] = None
-        elif t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=params.device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    pbuf, lbuf = (ctypes.c_double * nP)(*probs), (ctypes.c_double * max(nL, 1))(*levels)
-    a = _lib.DistributionArgs()
-    a.params, a.Tq, a.tq_stride = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT)
-    a.spot, a.rate, a.max_tail = _ptr(spot), float(rate), float(max_tail)
-    a.probs, a.nP = ctypes.cast(pbuf, ctypes.POINTER(ctypes.c_double)), nP
-    a.levels, a.nL = ctypes.cast(lbuf, ctypes.POINTER(ctypes.c_double)), nL
-    a.mT, a.B = mT, B
+    shapes = {"q_x": ((B, mT, nP), torch.float64, True), "q_strike": ((B, mT, nP), torch.float64, True),
+              "q_flags": ((B, mT, nP), torch.int32, True), "p_below": ((B, mT, nL), torch.float64, nL > 0),
+              "p_above": ((B, mT, nL), torch.float64, nL > 0), "tails": ((B, mT, 2), torch.float64, True),
+              "flags": ((B, mT), torch.int32, True)}
+    out = _outputs(torch, out, shapes, params.device)
+    a = _slice_fields(_lib.DistributionArgs(), params, Tq, spot, rate)
+    a.max_tail = float(max_tail)
+    a.probs, a.nP = _doubles(probs), nP
+    a.levels, a.nL = _doubles(levels), nL
     a.q_x, a.q_strike, a.q_flags = _ptr(out["q_x"]), _ptr(out["q_strike"]), _ptr(out["q_flags"])
     a.p_below, a.p_above, a.tails, a.flags = _ptr(out["p_below"]), _ptr(out["p_above"]), _ptr(out["tails"]), _ptr(out["flags"])
     a.rows_per_wave = int(rows_per_wave)
-    rc = lib.ivs_svi_distribution_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, params, Tq, spot, *out.values())
-    _lib.check(rc, "ivs_svi_distribution_f64")
-    return {k: out[k] for k in want}
-
-
-def _svi_inputs(torch, params, Tq, spot):
-    """The shared input checks of the stages that read SVI slices: params [B,mT,5], Tq [mT] or [B,mT], spot [B]."""
-    params = _f64(torch, params, "params"); Tq = _f64(torch, Tq, "Tq"); spot = _f64(torch, spot, "spot")
-    if params.dim() != 3 or params.shape[-1] != 5:
-        raise ValueError("params must be [B, mT, 5]")
-    B, mT, _ = params.shape
-    if Tq.dim() not in (1, 2) or Tq.shape[-1] != mT or (Tq.dim() == 2 and Tq.shape[0] != B):
-        raise ValueError("Tq must be [mT] or [B, mT]")
-    if spot.numel() != B:
-        raise ValueError("spot must hold one price per surface")
-    if mT > _lib.ST_MAX_TENORS:
-        raise ValueError(f"mT = {mT}: at most {_lib.ST_MAX_TENORS} tenors per snapshot are supported")
-    return params, Tq, spot, B, mT
+    _call(torch, "ivs_svi_distribution_f64", a, stream, params, Tq, spot, *out.values())
+    return {k: out[k] for k in shapes}
 
 
 def svi_calendar(params, Tq, spot, *, out=None, stream=None, rows_per_wave: int = 0):
@@ -588,27 +526,17 @@ def svi_calendar(params, Tq, spot, *, out=None, stream=None, rows_per_wave: int 
     are the same bit for bit).
     Returns dict(d_min, x_min, d_atm, x_cross, n_cross, flags) of device tensors; the flags are the _lib.SC_* bits."""
     torch = require_device()
-    lib = _lib.load()
     params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
-    out = dict(out or {})
-    want = {"d_min": ((B, mT), torch.float64), "x_min": ((B, mT), torch.float64), "d_atm": ((B, mT), torch.float64),
-            "x_cross": ((B, mT, 2), torch.float64), "n_cross": ((B, mT), torch.int32), "flags": ((B, mT), torch.int32)}
-    for k, (shape, dt) in want.items():
-        t = out.get(k)
-        if t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=params.device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    a = _lib.CalendarArgs()
-    a.params, a.Tq, a.tq_stride, a.spot = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot)
-    a.mT, a.B = mT, B
+    shapes = {"d_min": ((B, mT), torch.float64, True), "x_min": ((B, mT), torch.float64, True),
+              "d_atm": ((B, mT), torch.float64, True), "x_cross": ((B, mT, 2), torch.float64, True),
+              "n_cross": ((B, mT), torch.int32, True), "flags": ((B, mT), torch.int32, True)}
+    out = _outputs(torch, out, shapes, params.device)
+    a = _slice_fields(_lib.CalendarArgs(), params, Tq, spot)
     a.d_min, a.x_min, a.d_atm, a.x_cross = _ptr(out["d_min"]), _ptr(out["x_min"]), _ptr(out["d_atm"]), _ptr(out["x_cross"])
     a.n_cross, a.flags = _ptr(out["n_cross"]), _ptr(out["flags"])
     a.rows_per_wave = int(rows_per_wave)
-    rc = lib.ivs_svi_calendar_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, params, Tq, spot, *out.values())
-    _lib.check(rc, "ivs_svi_calendar_f64")
-    return {k: out[k] for k in want}
+    _call(torch, "ivs_svi_calendar_f64", a, stream, params, Tq, spot, *out.values())
+    return {k: out[k] for k in shapes}
 
 
 EVAL_OUTPUTS = ("w", "vol", "call", "put", "fwd_var", "g", "local_vol")
@@ -624,37 +552,18 @@ def svi_eval(params, Tq, spot, rate, u, tau, *, strike_mode: int = 0, want=EVAL_
     Returns dict(w, vol, call, put, fwd_var, g, local_vol, flags) of device tensors; the flags are the _lib.SE_* bits."""
     if strike_mode not in (0, 1):
         raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
-    want = tuple(want)
-    if any(k not in EVAL_OUTPUTS for k in want):
-        raise ValueError(f"want must name outputs among {EVAL_OUTPUTS}, got {want!r}")
+    want = _wanted(want, EVAL_OUTPUTS)
     torch = require_device()
-    lib = _lib.load()
     params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
-    u = _f64(torch, u, "u"); tau = _f64(torch, tau, "tau")
-    if u.dim() not in (1, 2) or u.shape != tau.shape or (u.dim() == 2 and u.shape[0] != B):
-        raise ValueError("u and tau must both be [Q] or both [B, Q]")
-    Q = u.shape[-1]
-    out = dict(out or {})
+    u, tau, _, _, Q = _option_queries(torch, B, u, tau, None)
     shapes = {k: ((B, Q), torch.float64, k in want) for k in EVAL_OUTPUTS}
     shapes["flags"] = ((B, Q), torch.int32, True)
-    for k, (shape, dt, on) in shapes.items():
-        t = out.get(k)
-        if not on:
-            out[k] = None
-        elif t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=params.device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    a = _lib.EvalArgs()
-    a.params, a.Tq, a.tq_stride, a.spot, a.rate = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
-    a.u, a.tau, a.q_stride, a.strike_mode = _ptr(u), _ptr(tau), (0 if u.dim() == 1 else Q), int(strike_mode)
-    a.mT, a.Q, a.B = mT, Q, B
-    for k in EVAL_OUTPUTS:
+    out = _outputs(torch, out, shapes, params.device)
+    a = _slice_fields(_lib.EvalArgs(), params, Tq, spot, rate)
+    _query_fields(a, u, tau, strike_mode)
+    for k in shapes:
         setattr(a, k, _ptr(out[k]))
-    a.flags = _ptr(out["flags"])
-    rc = lib.ivs_svi_eval_f64(a, None, 0, _stream(torch, stream))
-    _hold_for_stream(torch, stream, params, Tq, spot, u, tau, *out.values())
-    _lib.check(rc, "ivs_svi_eval_f64")
+    _call(torch, "ivs_svi_eval_f64", a, stream, params, Tq, spot, u, tau, *out.values())
     return {k: out[k] for k in shapes}
 
 
@@ -685,19 +594,6 @@ def _option_queries(torch, B, u, tau, is_put, qty=None):
     return u, tau, is_put, qty, Q
 
 
-def _outputs(torch, out, shapes, device):
-    out = dict(out or {})
-    for k, (shape, dt, on) in shapes.items():
-        t = out.get(k)
-        if not on:
-            out[k] = None
-        elif t is None:
-            out[k] = torch.empty(shape, dtype=dt, device=device)
-        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape}")
-    return out
-
-
 def svi_greeks(params, Tq, spot, rate, u, tau, *, is_put=None, strike_mode: int = 0, want=GREEK_OUTPUTS, out=None, stream=None):
     """Smile-aware Greeks of options on the surface of the raw SVI slices (ivs_svi_greeks_f64; rules G0-G6 of DESIGN.md section
     17).  params, Tq, spot, rate, u, tau, strike_mode as in svi_eval; is_put uint8 / bool [Q] (one side per option, shared by
@@ -709,32 +605,24 @@ def svi_greeks(params, Tq, spot, rate, u, tau, *, is_put=None, strike_mode: int 
     _lib.SE_* bits SHORT, LONG, NEG_FWD, DEAD, UNORDERED."""
     if strike_mode not in (0, 1):
         raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
-    want = tuple(want)
-    if any(k not in GREEK_OUTPUTS for k in want):
-        raise ValueError(f"want must name outputs among {GREEK_OUTPUTS}, got {want!r}")
+    want = _wanted(want, GREEK_OUTPUTS)
     torch = require_device()
-    lib = _lib.load()
     params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
     u, tau, is_put, _, Q = _option_queries(torch, B, u, tau, is_put)
     shapes = {k: ((B, Q), torch.float64, k in want) for k in GREEK_OUTPUTS}
     shapes["flags"] = ((B, Q), torch.int32, True)
     out = _outputs(torch, out, shapes, params.device)
-    a = _lib.GreeksArgs()
-    a.params, a.Tq, a.tq_stride, a.spot, a.rate = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
-    a.u, a.tau, a.q_stride, a.strike_mode = _ptr(u), _ptr(tau), (0 if u.dim() == 1 else Q), int(strike_mode)
+    a = _slice_fields(_lib.GreeksArgs(), params, Tq, spot, rate)
+    _query_fields(a, u, tau, strike_mode)
     a.is_put = _ptr(is_put)
-    a.mT, a.Q, a.B = mT, Q, B
-    for k in GREEK_OUTPUTS:
+    for k in shapes:
         setattr(a, k, _ptr(out[k]))
-    a.flags = _ptr(out["flags"])
-    rc = lib.ivs_svi_greeks_f64(a, None, 0, _stream(torch, stream))
-    if rc == 0 and mT == 0:                                  # the C call is a no-op; without a slice every option is dead (E1)
+    _call(torch, "ivs_svi_greeks_f64", a, stream, params, Tq, spot, u, tau, is_put, *out.values())
+    if mT == 0:                                              # the C call is a no-op; without a slice every option is dead (E1)
         with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
             for k in want:
                 out[k].fill_(float("nan"))
             out["flags"].fill_(_lib.SE_DEAD)
-    _hold_for_stream(torch, stream, params, Tq, spot, u, tau, is_put, *out.values())
-    _lib.check(rc, "ivs_svi_greeks_f64")
     return {k: out[k] for k in shapes}
 
 
@@ -766,15 +654,11 @@ def svi_book(params, Tq, spot, rate, u, tau, qty, spot_shocks=DEFAULT_SPOT_SHOCK
     degenerate (NaN, n_dead = Q, cell flags 0), and a book without options has 0 in every sum, count and flag.
     Returns dict(net, n_dead, pnl_ss, pnl_sm, cell_flags) of device tensors; net's columns are NET_COLUMNS, the cell flags the
     _lib.SB_* bits."""
-    import ctypes
     if strike_mode not in (0, 1):
         raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
-    want = tuple(want)
-    if any(k not in BOOK_OUTPUTS for k in want):
-        raise ValueError(f"want must name outputs among {BOOK_OUTPUTS}, got {want!r}")
+    want = _wanted(want, BOOK_OUTPUTS)
     sa, sv = book_shocks(spot_shocks, vol_shocks)
     torch = require_device()
-    lib = _lib.load()
     params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
     u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
     nA, nV = len(sa), len(sv)
@@ -782,19 +666,16 @@ def svi_book(params, Tq, spot, rate, u, tau, qty, spot_shocks=DEFAULT_SPOT_SHOCK
               "pnl_ss": ((B, nA, nV), torch.float64, "pnl_ss" in want), "pnl_sm": ((B, nA, nV), torch.float64, "pnl_sm" in want),
               "cell_flags": ((B, nA, nV), torch.int32, True)}
     out = _outputs(torch, out, shapes, params.device)
-    abuf, vbuf = (ctypes.c_double * max(nA, 1))(*sa), (ctypes.c_double * max(nV, 1))(*sv)
-    a = _lib.BookArgs()
-    a.params, a.Tq, a.tq_stride, a.spot, a.rate = _ptr(params), _ptr(Tq), (0 if Tq.dim() == 1 else mT), _ptr(spot), float(rate)
-    a.u, a.tau, a.q_stride, a.strike_mode = _ptr(u), _ptr(tau), (0 if u.dim() == 1 else Q), int(strike_mode)
+    a = _slice_fields(_lib.BookArgs(), params, Tq, spot, rate)
+    _query_fields(a, u, tau, strike_mode)
     a.is_put, a.qty = _ptr(is_put), _ptr(qty)
-    a.mT, a.Q, a.B = mT, Q, B
-    a.spot_shocks, a.nA = ctypes.cast(abuf, ctypes.POINTER(ctypes.c_double)), nA
-    a.vol_shocks, a.nV = ctypes.cast(vbuf, ctypes.POINTER(ctypes.c_double)), nV
-    a.net, a.n_dead, a.cell_flags = _ptr(out["net"]), _ptr(out["n_dead"]), _ptr(out["cell_flags"])
-    a.pnl_ss, a.pnl_sm = _ptr(out["pnl_ss"]), _ptr(out["pnl_sm"])
+    a.spot_shocks, a.nA = _doubles(sa), nA
+    a.vol_shocks, a.nV = _doubles(sv), nV
+    for k in shapes:
+        setattr(a, k, _ptr(out[k]))
     a.cells_per_wg = int(cells_per_wg)
-    rc = lib.ivs_svi_book_f64(a, None, 0, _stream(torch, stream))
-    if rc == 0 and B > 0 and (mT == 0 or Q == 0):            # the C call is a no-op: the result is defined here
+    _call(torch, "ivs_svi_book_f64", a, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
+    if B > 0 and (mT == 0 or Q == 0):                        # the C call is a no-op: the result is defined here
         empty = float("nan") if mT == 0 else 0.0             # B1: no live slice -> NaN and n_dead = Q; a book without options is worth 0
         with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
             out["net"].fill_(empty)
@@ -802,8 +683,6 @@ def svi_book(params, Tq, spot, rate, u, tau, qty, spot_shocks=DEFAULT_SPOT_SHOCK
             out["cell_flags"].zero_()
             for k in want:
                 out[k].fill_(empty)
-    _hold_for_stream(torch, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
-    _lib.check(rc, "ivs_svi_book_f64")
     return {k: out[k] for k in shapes}
 
 
@@ -1041,23 +920,6 @@ def _option_inputs(torch, tensors, names, is_put):
     return ins, n, is_put
 
 
-def _option_outputs(torch, out, want, like):
-    """`want`: key -> (dtype, on).  Outputs of like's shape, taken from `out` (checked) or allocated; None where off."""
-    out = dict(out or {})
-    res = {}
-    for k, (dt, on) in want.items():
-        t = out.get(k)
-        if not on:
-            res[k] = None
-        elif t is None:
-            res[k] = torch.empty(like.shape, dtype=dt, device=like.device)
-        elif t.numel() != like.numel() or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor with one entry per option")
-        else:
-            res[k] = t
-    return res
-
-
 def bs_price(S, K, T, r, sigma, is_put=None, default_is_put: bool = False, want_vega: bool = False, out=None, stream=None,
              want_flags: bool = True):
     """Black-Scholes prices on the device (ivs_bs_price_f64; rules V1, V8 of DESIGN.md section 16).  All inputs CUDA float64
@@ -1068,8 +930,11 @@ def bs_price(S, K, T, r, sigma, is_put=None, default_is_put: bool = False, want_
     torch = require_device()
     lib = _lib.load()
     ins, n, is_put = _option_inputs(torch, (S, K, T, r, sigma), ("S", "K", "T", "r", "sigma"), is_put)
-    res = _option_outputs(torch, out, {"price": (torch.float64, True), "vega": (torch.float64, bool(want_vega)),
-                                       "flags": (torch.int32, bool(want_flags))}, ins[0])
+    shape = tuple(ins[0].shape)
+    shapes = {"price": (shape, torch.float64, True), "vega": (shape, torch.float64, bool(want_vega)),
+              "flags": (shape, torch.int32, bool(want_flags))}
+    out = _outputs(torch, out, shapes, ins[0].device, per_option=True)
+    res = {k: out[k] for k in shapes}
     rc = lib.ivs_bs_price_f64(*[_ptr(t) for t in ins], _ptr(is_put), int(bool(default_is_put)), n,
                               _ptr(res["price"]), _ptr(res["vega"]), _ptr(res["flags"]), _stream(torch, stream))
     _hold_for_stream(torch, stream, *ins, is_put, *res.values())
@@ -1091,7 +956,10 @@ def bs_implied_vol(price, S, K, T, r, is_put=None, default_is_put: bool = False,
     torch = require_device()
     lib = _lib.load()
     ins, n, is_put = _option_inputs(torch, (price, S, K, T, r), ("price", "S", "K", "T", "r"), is_put)
-    res = _option_outputs(torch, out, {"vol": (torch.float64, True), "flags": (torch.int32, True)}, ins[0])
+    shape = tuple(ins[0].shape)
+    shapes = {"vol": (shape, torch.float64, True), "flags": (shape, torch.int32, True)}
+    out = _outputs(torch, out, shapes, ins[0].device, per_option=True)
+    res = {k: out[k] for k in shapes}
     rc = lib.ivs_bs_implied_vol_f64(*[_ptr(t) for t in ins], _ptr(is_put), int(bool(default_is_put)), int(price_mode), n,
                                     _ptr(res["vol"]), _ptr(res["flags"]), _stream(torch, stream))
     _hold_for_stream(torch, stream, *ins, is_put, *res.values())

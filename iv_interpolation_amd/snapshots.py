@@ -38,7 +38,7 @@ from typing import List, Sequence, Union
 import numpy as np
 import pandas as pd
 
-from . import synth
+from . import engine, synth
 from .engine import DEFAULT_DELTAS, delta_targets      # rule D3: 10d put, 25d put, ATM, 25d call, 10d call
 from .engine import DEFAULT_LEVELS, DEFAULT_PROBS, distribution_targets   # rule P9 and the host-side checks of section 13
 
@@ -241,80 +241,63 @@ class HipBackend:
     def __init__(self, stream=None):
         self.stream = stream
 
-    def assemble(self, date_ns, iv, underlying, row_off, cells, strikes, expiry_ns, t0_ns, n_snapshots, moneyness, kq_empty):
-        from . import engine
+    @staticmethod
+    def _up(a, dtype=None):
+        """A host array on the current HIP device (dtype None keeps the array's own)."""
         torch = engine.require_device()
-        d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+        return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
+
+    def assemble(self, date_ns, iv, underlying, row_off, cells, strikes, expiry_ns, t0_ns, n_snapshots, moneyness, kq_empty):
+        d = self._up
         return engine.snapshot_assemble(d(date_ns), d(iv), d(underlying), d(row_off), d(cells), d(strikes), d(expiry_ns),
                                         t0_ns, n_snapshots, d(moneyness), kq_empty, stream=self.stream)
 
     def surface_batch(self, K, T, sigma, Kq, Tq, method):
-        from . import engine
-        torch = engine.require_device()
-        return engine.surface_batch(torch.from_numpy(np.ascontiguousarray(K)).cuda(), T, sigma, Kq,
-                                    torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), method, stream=self.stream)
+        return engine.surface_batch(self._up(K), T, sigma, Kq, self._up(Tq), method, stream=self.stream)
 
     def smile_points(self, vol, Kq, Tq, spot, deltas, rate):
-        from . import engine
-        torch = engine.require_device()
-        return engine.smile_delta_points(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, deltas, rate,
-                                         stream=self.stream)
+        Tq = self._up(Tq)
+        return engine.smile_delta_points(vol, Kq, Tq, spot, deltas, rate, stream=self.stream)
 
     def arbitrage(self, vol, Kq, Tq, spot, rate):
-        from . import engine
-        torch = engine.require_device()
-        return engine.surface_arbitrage(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate,
-                                        stream=self.stream)
+        Tq = self._up(Tq)
+        return engine.surface_arbitrage(vol, Kq, Tq, spot, rate, stream=self.stream)
 
     def moments(self, vol, Kq, Tq, spot, rate, horizons, min_mass):
-        from . import engine
-        torch = engine.require_device()
-        return engine.surface_moments(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate,
-                                      horizons=horizons, min_mass=min_mass, stream=self.stream)
+        Tq = self._up(Tq)
+        return engine.surface_moments(vol, Kq, Tq, spot, rate, horizons=horizons, min_mass=min_mass, stream=self.stream)
 
     def svi(self, vol, Kq, Tq, spot, rate, rounds, fitted):
-        from . import engine
-        torch = engine.require_device()
-        return engine.svi_slices(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, rounds=rounds,
-                                 fitted=fitted, stream=self.stream)
+        Tq = self._up(Tq)
+        return engine.svi_slices(vol, Kq, Tq, spot, rate, rounds=rounds, fitted=fitted, stream=self.stream)
 
     def ssvi(self, vol, Kq, Tq, spot, rate, raw, theta0, rounds, fitted):
-        from . import engine
-        torch = engine.require_device()
-        return engine.ssvi_surface(vol, Kq, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, raw=raw, theta0=theta0,
-                                   rounds=rounds, fitted=fitted, stream=self.stream)
+        Tq = self._up(Tq)
+        return engine.ssvi_surface(vol, Kq, Tq, spot, rate, raw=raw, theta0=theta0, rounds=rounds, fitted=fitted,
+                                   stream=self.stream)
 
     def distribution(self, params, Tq, spot, rate, probs, levels, max_tail):
-        from . import engine
-        torch = engine.require_device()
-        return engine.svi_distribution(params, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, rate, probs=probs,
-                                       levels=levels, max_tail=max_tail, stream=self.stream)
+        Tq = self._up(Tq)
+        return engine.svi_distribution(params, Tq, spot, rate, probs=probs, levels=levels, max_tail=max_tail,
+                                       stream=self.stream)
 
     def calendar(self, params, Tq, spot):
-        from . import engine
-        torch = engine.require_device()
-        return engine.svi_calendar(params, torch.from_numpy(np.ascontiguousarray(Tq)).cuda(), spot, stream=self.stream)
+        Tq = self._up(Tq)
+        return engine.svi_calendar(params, Tq, spot, stream=self.stream)
 
     def evaluate(self, params, Tq, spot, rate, u, tau, strike_mode):
-        from . import engine
-        torch = engine.require_device()
-        d = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()  # noqa: E731
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
         return engine.svi_eval(params, d(Tq), spot, rate, d(u), d(tau), strike_mode=strike_mode, stream=self.stream)
 
     def greeks(self, params, Tq, spot, rate, u, tau, is_put, strike_mode):
-        from . import engine
-        torch = engine.require_device()
-        d = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()  # noqa: E731
-        side = torch.from_numpy(np.ascontiguousarray(is_put, np.uint8)).cuda()
-        return engine.svi_greeks(params, d(Tq), spot, rate, d(u), d(tau), is_put=side, strike_mode=strike_mode, stream=self.stream)
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
+        return engine.svi_greeks(params, d(Tq), spot, rate, d(u), d(tau), is_put=self._up(is_put, np.uint8),
+                                 strike_mode=strike_mode, stream=self.stream)
 
     def book(self, params, Tq, spot, rate, u, tau, qty, spot_shocks, vol_shocks, is_put, strike_mode):
-        from . import engine
-        torch = engine.require_device()
-        d = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()  # noqa: E731
-        side = torch.from_numpy(np.ascontiguousarray(is_put, np.uint8)).cuda()
-        return engine.svi_book(params, d(Tq), spot, rate, d(u), d(tau), d(qty), spot_shocks, vol_shocks, is_put=side,
-                               strike_mode=strike_mode, stream=self.stream)
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
+        return engine.svi_book(params, d(Tq), spot, rate, d(u), d(tau), d(qty), spot_shocks, vol_shocks,
+                               is_put=self._up(is_put, np.uint8), strike_mode=strike_mode, stream=self.stream)
 
 
 def _host(a):
@@ -529,10 +512,7 @@ class SnapshotSurfaceBuilder:
         [0, 1]; ValueError outside."""
         probs, levels = distribution_targets(DEFAULT_PROBS if probs is None else probs,
                                              DEFAULT_LEVELS if levels is None else levels, max_tail)
-        if svi_reports is None:
-            svi_reports = self.svi(results, rate=rate, rounds=rounds)
-        if len(svi_reports) != len(results):
-            raise ValueError(f"{len(svi_reports)} SVI reports for {len(results)} surfaces")
+        svi_reports = self._slices(results, svi_reports, rate, rounds)
         be = self._backend or HipBackend()
         reports = []
         for r, v in zip(results, svi_reports):
@@ -549,6 +529,20 @@ class SnapshotSurfaceBuilder:
         if len(svi_reports) != len(results):
             raise ValueError(f"{len(svi_reports)} SVI reports for {len(results)} surfaces")
         return svi_reports
+
+    @staticmethod
+    def _tau(expiry: pd.DatetimeIndex, dates: pd.DatetimeIndex) -> np.ndarray:
+        """Years from every snapshot date to every expiry, [B, Q]; naive expiries are read in the time zone of the snapshots,
+        a missing expiry gives NaN."""
+        e = expiry
+        if e.tz is None and dates.tz is not None:
+            e = e.tz_localize(dates.tz)
+        elif e.tz is not None and dates.tz is None:
+            e = e.tz_convert("UTC").tz_localize(None)
+        e_ns, d_ns = e.as_unit("ns").asi8, dates.as_unit("ns").asi8
+        tau = (e_ns[None, :] - d_ns[:, None]).astype(np.float64) / float(YEAR_NS)
+        tau[:, np.asarray(e.isna())] = np.nan
+        return tau
 
     def calendar(self, results: Sequence[SnapshotSurfaces], svi_reports=None, rate: float = 0.0, rounds: int = 0) -> List[CalendarReport]:
         """Calendar report between the SVI slices of every surface of `results` (rules T1-T4, C1-C6): one CalendarReport per
@@ -579,14 +573,7 @@ class SnapshotSurfaceBuilder:
         be = self._backend or HipBackend()
         reports = []
         for r, v in zip(results, svi_reports):
-            e = expiry
-            if e.tz is None and r.dates.tz is not None:
-                e = e.tz_localize(r.dates.tz)
-            elif e.tz is not None and r.dates.tz is None:
-                e = e.tz_convert("UTC").tz_localize(None)
-            e_ns, d_ns = e.as_unit("ns").asi8, r.dates.as_unit("ns").asi8
-            tau = (e_ns[None, :] - d_ns[:, None]).astype(np.float64) / float(YEAR_NS)
-            tau[:, np.asarray(e.isna())] = np.nan
+            tau = self._tau(expiry, r.dates)
             u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
             q = be.evaluate(v.params, r.tenors, r.spot, float(rate), u, tau, 1)
             reports.append(PriceReport(r.underlying, r.dates, strikes, expiry, tau, float(rate), q["w"], q["vol"], q["call"], q["put"],
@@ -619,14 +606,7 @@ class SnapshotSurfaceBuilder:
         be = self._backend or HipBackend()
         reports = []
         for r, v in zip(results, svi_reports):
-            e = expiry
-            if e.tz is None and r.dates.tz is not None:
-                e = e.tz_localize(r.dates.tz)
-            elif e.tz is not None and r.dates.tz is None:
-                e = e.tz_convert("UTC").tz_localize(None)
-            e_ns, d_ns = e.as_unit("ns").asi8, r.dates.as_unit("ns").asi8
-            tau = (e_ns[None, :] - d_ns[:, None]).astype(np.float64) / float(YEAR_NS)
-            tau[:, np.asarray(e.isna())] = np.nan
+            tau = self._tau(expiry, r.dates)
             u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
             g = be.greeks(v.params, r.tenors, r.spot, float(rate), u, tau, is_put, 1)
             k = be.book(v.params, r.tenors, r.spot, float(rate), u, tau, qty, sa, sv, is_put, 1)
