@@ -180,6 +180,10 @@ int ivs_frame_rows(const int64_t* q_off, int64_t n_series, int64_t total_queries
  *                                                   ivs_interp1d_greeks_batch_f64 with validity rows in place of fill_idx
  *                                                   rows; greeks == NULL: no epilogue
  *   workspace   ivs_frame_workspace_bytes(total_src, S, C) bytes
+ *
+ * Per series: any number of source rows and valid knots gives the same results.  The staged forms of the pass keep knot ranks
+ * and counts in 16 bits, so a block that touches a series of more than 65 535 source rows always takes the per-row path on
+ * the global arrays (the cost of the separate calls for those blocks); total_src is limited to 2^31 - 1.
  */
 typedef struct ivs_frame_args {
     const int64_t* src_pos; const int64_t* src_off; const int64_t* q_off;

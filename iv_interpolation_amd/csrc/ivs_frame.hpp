@@ -14,7 +14,7 @@
 //     walks one step;
 //   * every f64 column leaves as 16-byte stores, 1 KiB contiguous per wave instruction.
 // Blocks whose symbols exceed the staging limits (FR_CAP source rows, FR_MAXSYM symbols, FR_MAXV / FR_MAXF / FR_MAXCC
-// columns) take a per-row path on the global arrays: same results, the old cost.
+// columns, FR_MAXKNOTS source rows in one symbol) take a per-row path on the global arrays: same results, the old cost.
 #pragma once
 #include "ivs_interp1d.hpp"
 
@@ -33,6 +33,7 @@ constexpr int FR_ROWS = 256 * 2 * FR_UNITS;      // rows per block
 constexpr int FR_CAP = IVS_FR_CAP;
 static_assert(FR_CAP <= 256 && FR_CAP % 16 == 0, "one staged source row per thread; 16-byte aligned column rows");
 constexpr int FR_MAXSYM = 64;             // symbols per block on the staged path
+constexpr int FR_MAXKNOTS = 65535;        // source rows of a symbol on the window form (16-bit knot ranks and counts)
 constexpr int FR_MAXV = 16;               // validity rows (forward-filled columns + the three Greek inputs)
 constexpr int FR_MAXC = 3;                // channels
 constexpr int FR_MAXF = 8;                // forward-filled f64 columns
@@ -427,7 +428,11 @@ __global__ __launch_bounds__(256) void frame_fused_kernel(FrameParams f, Interp1
             const int64_t pos = (tid ? g_last : g0) - f.q_off[s];
             int64_t x0 = 0, x1 = n;
             while (x0 < x1) { const int64_t m = (x0 + x1) >> 1; if (f.src_pos[a + m] <= pos) x0 = m + 1; else x1 = m; }
-            sh.s_edge[2 + (tid ? 1 : 0)] = tid ? a + x0 : a + (x0 > 0 ? x0 - 1 : 0);      // W1x (exclusive) / W0
+            // s_rank / y_n hold 16 bits.  Only the block's first and last symbol can have more knots than the window has rows
+            // (every symbol between them lies wholly inside it), and a symbol has no more knots than source rows: one of more
+            // than FR_MAXKNOTS rows keeps its whole range, which exceeds FR_CAP, and the block takes the per-row path
+            const bool wide = n > FR_MAXKNOTS;
+            sh.s_edge[2 + (tid ? 1 : 0)] = wide ? (tid ? a + n : a) : (tid ? a + x0 : a + (x0 > 0 ? x0 - 1 : 0));      // W1x (exclusive) / W0
         }
         __syncthreads();
         W0 = sh.s_edge[2]; W1x = sh.s_edge[3];

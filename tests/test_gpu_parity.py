@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import ivs_oracle as O  # noqa: E402
 from golden_io import method_tolerances  # noqa: F401
 from golden_io import GOLDEN, SymbolCases, assert_symbol_frame  # noqa: E402
+from interp1d_forms_cases import fill_columns  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -957,13 +958,50 @@ def test_fused_frame_pass_fuzz(method, seed, profile):
     _fused_frame_case(method, 1000 * seed + len(profile), profile)
 
 
+def fused_equals_separate(case, method, greeks=True, C=3):
+    """ivs_frame_columns_f64 on a frame case (interp1d_forms_cases.fill_columns) against the five calls it replaces, bit for bit;
+    with or without the Greeks epilogue (which needs the three channels).  Returns the fused pass's channels [C, total_q]."""
+    import torch
+    from iv_interpolation_amd import engine
+    d = dev
+    k = case
+    total_q, nV = int(k["q_off"][-1]), k["valid"].shape[0]
+    ko, qo, pos_d, yk_d = d(k["src_off"]), d(k["q_off"]), d(k["pos"]), d(k["yk"][:C])
+    valid, needs, first_ns = d(k["valid"]), d(k["needs"][:, :C]), d(k["first_ns"])
+    fsrc, f_rows, csrc, c_rows = d(k["fsrc"]), d(k["f_rows"]), d(k["csrc"]), d(k["c_rows"])
+    vall = d(np.concatenate([k["valid"], k["gvalid"]])) if greeks else valid
+    greek = ((nV, nV + 1, nV + 2), d(k["ksrc"]), d(k["rsrc"]), d(k["psrc"])) if greeks else None
+    got = engine.frame_columns(pos_d, ko, qo, total_q, yk_d, method, vall, fsrc, f_rows, csrc, c_rows, d(k["host_rows"]),
+                               first_ns, needs, 0, greek)
+    torch.cuda.synchronize()
+    fidx = engine.ffill_index_batch(pos_d, ko, valid, qo, total_q)
+    if greeks:
+        gidx = engine.ffill_index_batch(pos_d, ko, d(k["gvalid"]), qo, total_q)
+        out, st, gr = engine.interp1d_greeks_batch(pos_d.to(torch.float64), yk_d, ko, qo, total_q, method, (0, 1, 2), gidx, (0, 1, 2),
+                                                   d(k["ksrc"]), d(k["rsrc"]), d(k["psrc"]))
+    else:
+        out, st = engine.interp1d_batch(pos_d.to(torch.float64), yk_d, ko, qo, total_q, method)
+    F = engine.gather_rows(fsrc, fidx, f_rows); Cc = engine.gather_rows(csrc, fidx, c_rows)
+    dts, kp = engine.frame_rows(qo, first_ns, out, Cc[0], st, needs)
+    torch.cuda.synchronize()
+    eq = lambda a, b: np.array_equal(a.cpu().numpy(), b.cpu().numpy(), equal_nan=True)      # noqa: E731
+    assert eq(got["status"], st)
+    assert eq(got["chan"], out), method
+    assert eq(got["F"], F) and eq(got["C"], Cc)
+    assert eq(got["idx"], fidx[torch.from_numpy(k["host_rows"].astype(np.int64)).cuda()])
+    assert eq(got["date_ns"], dts) and eq(got["keep"], kp)
+    if greeks:
+        assert eq(got["greeks"], gr)
+    else:
+        assert got["greeks"] is None
+    return got["chan"].cpu().numpy()
+
+
 def _fused_frame_case(method, seed, profile):
     """ivs_frame_columns_f64 (one pass over the output rows) against the five calls it replaces -- interp1d[_greeks]_batch,
     ffill_index_batch, gather_rows x2, frame_rows -- bit for bit: symbols of 1..700 source rows (beyond 512 staged rows a
     block takes the per-row path), tiny symbols (many per block), sparse validity, a first source row that is NOT at
     position 0, duplicate-style consecutive positions, and the Greeks epilogue."""
-    import torch
-    from iv_interpolation_amd import engine
     r = np.random.default_rng(seed)
     if profile == "dense":
         sizes = np.concatenate([r.integers(150, 900, 12), r.integers(1, 40, 30)]); gap_set = [1, 1, 1, 2, 3]
@@ -987,38 +1025,10 @@ def _fused_frame_case(method, seed, profile):
     yk = r.normal(0.6, 0.1, (3, n_src)); yk[1] = 25000 + 100 * yk[1]; yk[2] = np.abs(yk[2]) * 0.1 + 0.01
     yk[r.random(yk.shape) < 0.25] = np.nan
     yk[0, src_off[7]:src_off[8]] = np.nan
-    nV = 9
-    valid = (r.random((nV, n_src)) > 0.3).astype(np.uint8); valid[4] = 0; valid[5] = 1
-    fsrc = r.normal(size=(5, n_src)); f_rows = np.array([1, 2, 3, 4, 5], np.int32)
-    csrc = r.integers(0, 50, (2, n_src)).astype(np.int32); c_rows = np.array([0, 6], np.int32)
-    host_rows = np.array([7, 8], np.int32)
-    first_ns = (r.integers(0, 10**6, S) * 60_000_000_000).astype(np.int64)
-    needs = (r.random((S, 3)) < 0.7).astype(np.uint8)
-    gvalid = (r.random((3, n_src)) > 0.2).astype(np.uint8)
-    ksrc = r.uniform(20000, 30000, n_src); rsrc = r.uniform(0, 0.05, n_src); psrc = r.integers(0, 3, n_src).astype(np.uint8)
-    d = dev
-    ko, qo, pos_d, yk_d = d(src_off), d(q_off), d(pos), d(yk)
-    vall = np.concatenate([valid, gvalid])
-    got = engine.frame_columns(pos_d, ko, qo, total_q, yk_d, method, d(vall), d(fsrc), d(f_rows), d(csrc), d(c_rows), d(host_rows),
-                               d(first_ns), d(needs), 0, ((nV, nV + 1, nV + 2), d(ksrc), d(rsrc), d(psrc)))
-    torch.cuda.synchronize()
-    fidx = engine.ffill_index_batch(pos_d, ko, d(valid), qo, total_q)
-    gidx = engine.ffill_index_batch(pos_d, ko, d(gvalid), qo, total_q)
-    out, st, gr = engine.interp1d_greeks_batch(pos_d.to(torch.float64), yk_d, ko, qo, total_q, method, (0, 1, 2), gidx, (0, 1, 2),
-                                               d(ksrc), d(rsrc), d(psrc))
-    F = engine.gather_rows(d(fsrc), fidx, d(f_rows)); Cc = engine.gather_rows(d(csrc), fidx, d(c_rows))
-    dts, kp = engine.frame_rows(qo, d(first_ns), out, Cc[0], st, d(needs))
-    torch.cuda.synchronize()
-    eq = lambda a, b: np.array_equal(a.cpu().numpy(), b.cpu().numpy(), equal_nan=True)      # noqa: E731
-    assert eq(got["status"], st)
-    assert eq(got["chan"], out), method
-    assert eq(got["F"], F) and eq(got["C"], Cc)
-    assert eq(got["idx"], fidx[torch.from_numpy(host_rows.astype(np.int64)).cuda()])
-    assert eq(got["date_ns"], dts) and eq(got["keep"], kp)
-    assert eq(got["greeks"], gr)
+    case = dict(src_off=src_off, q_off=q_off, pos=pos, yk=yk, **fill_columns(r, n_src, S))
+    g = fused_equals_separate(case, method)
     # and the channels against the oracle (the separate calls are pinned elsewhere; this pins the fused pass directly)
     ref, rst = O.interp1d_batch(pos.astype(np.float64), yk, src_off, None, q_off, O.METHOD_CODES[method])
-    g = got["chan"].cpu().numpy()
     ks = np.repeat(np.arange(S), sizes); gpos = q_off[:-1][ks] + pos
     for c in range(3):                                            # knot rows keep their source cell in `chan` ...
         okk = ~np.isnan(yk[c]) & (rst[ks, c] != O.ST_ILL_CONDITIONED)      # ... unless the polynomial was refused (> 32 knots)
