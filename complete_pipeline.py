@@ -36,6 +36,7 @@ CALENDAR_TABLE = "iv_calendar"
 SSVI_TABLE = "iv_ssvi"
 IMPLIED_TABLE = "iv_implied"
 RISK_TABLE = "iv_risk"
+EXPLAIN_TABLE = "iv_explain"
 SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
@@ -330,6 +331,30 @@ class CompleteOptimizedPipeline:
         return {"success": n_rows > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "duration": duration}
 
+    @staticmethod
+    def _book(frames, book_file: Optional[str]):
+        """The book of run_risk and run_explain: every listed contract of the chain with quantity +1, or the CSV `book_file`
+        (symbol, quantity) joined to it.  Returns (book, None) or (None, what is wrong with the file)."""
+        from iv_interpolation_amd.snapshots import listed_book
+        book = listed_book(frames)
+        if book_file:
+            held = pd.read_csv(book_file)
+            for c in ("symbol", "quantity"):
+                if c not in held.columns:
+                    return None, f"{book_file}: no column {c!r}"
+            held = held.assign(symbol=held["symbol"].astype(str), quantity=pd.to_numeric(held["quantity"], errors="coerce"))
+            unknown = sorted(set(held["symbol"]) - set(book["symbol"]))
+            if unknown:
+                return None, f"{book_file}: not listed in the chain: {unknown[:4]}"
+            twice = sorted(set(held["symbol"][held["symbol"].duplicated()]))
+            if twice:
+                return None, f"{book_file}: listed more than once: {twice[:4]}"
+            bad = held["symbol"][~np.isfinite(held["quantity"].to_numpy(np.float64))].tolist()
+            if bad:
+                return None, f"{book_file}: the quantity is not a finite number: {bad[:4]}"
+            book = book.drop(columns="quantity").merge(held[["symbol", "quantity"]], on="symbol", how="inner")
+        return book, None
+
     def run_risk(self, book_file: Optional[str] = None) -> dict:
         """Book risk: the snapshots of run_surfaces and the slices of run_svi, then the smile-aware
         Greeks of a book of options, its net Greeks and its scenario P&L grid per snapshot on the device.  The book is every
@@ -339,30 +364,16 @@ class CompleteOptimizedPipeline:
         delta_ss, delta_sm, gamma_ss, gamma_sm, vega, theta, gross, n_dead) and one `iv_scenarios` table (columns underlying,
         date, spot, spot_shock, vol_shock, dynamic, pnl, flags) per underlying."""
         from iv_interpolation_amd import _lib
-        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, listed_book, risk_frame, scenario_frame
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, risk_frame, scenario_frame
         print("\nRISK: SMILE-AWARE GREEKS AND SCENARIO P&L OF A BOOK (MI355X engine)")
         print("-" * 40)
         frames = self._interpolated_frames()
         if not frames:
             return {"success": False, "error": "No interpolated data found for the book risk"}
         start = time.time()
-        book = listed_book(frames)
-        if book_file:
-            held = pd.read_csv(book_file)
-            for c in ("symbol", "quantity"):
-                if c not in held.columns:
-                    return {"success": False, "error": f"{book_file}: no column {c!r}"}
-            held = held.assign(symbol=held["symbol"].astype(str), quantity=pd.to_numeric(held["quantity"], errors="coerce"))
-            unknown = sorted(set(held["symbol"]) - set(book["symbol"]))
-            if unknown:
-                return {"success": False, "error": f"{book_file}: not listed in the chain: {unknown[:4]}"}
-            twice = sorted(set(held["symbol"][held["symbol"].duplicated()]))
-            if twice:
-                return {"success": False, "error": f"{book_file}: listed more than once: {twice[:4]}"}
-            bad = held["symbol"][~np.isfinite(held["quantity"].to_numpy(np.float64))].tolist()
-            if bad:
-                return {"success": False, "error": f"{book_file}: the quantity is not a finite number: {bad[:4]}"}
-            book = book.drop(columns="quantity").merge(held[["symbol", "quantity"]], on="symbol", how="inner")
+        book, error = self._book(frames, book_file)
+        if error:
+            return {"success": False, "error": error}
         builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
         results = builder.build(frames)
         n_rows = n_fit = n_bf = n_risk = n_scen = n_dead = 0
@@ -388,6 +399,57 @@ class CompleteOptimizedPipeline:
         print(f"\nRISK COMPLETE: {duration:.1f}s, underlyings {len(results)}, snapshots {n_risk:,}, scenario rows {n_scen:,}, dead {n_dead:,}")
         return {"success": n_risk > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "risk_rows": n_risk, "scenario_rows": n_scen, "dead_options": n_dead, "duration": duration}
+
+    def run_explain(self, book_file: Optional[str] = None, lag: int = 1) -> dict:
+        """P&L explain: the snapshots of run_surfaces and the slices of run_svi, then the P&L of a book
+        of options between every snapshot and the one `lag` snapshots later, split into theta, delta, gamma, vega and a
+        remainder under sticky strike and under sticky moneyness, on the device.  The book is run_risk's.  One `iv_explain`
+        table per underlying (columns underlying, start, end, dS, actual, theta_pnl, delta_ss, gamma_ss, vega_ss, resid_ss,
+        delta_sm, gamma_sm, vega_sm, resid_sm, value, gross, n_dead).  Besides run_svi's keys the result has explain_rows,
+        dead_options and, per dynamic, unexplained_ss / unexplained_sm: the sum of |net remainder| over the sum of |net actual|
+        over the pairs with a finite net (NaN without one): the dynamic with the smaller figure explains the chain better."""
+        from iv_interpolation_amd import _lib
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, explain_frame
+        print("\nEXPLAIN: P&L OF A BOOK BETWEEN SNAPSHOTS UNDER BOTH SMILE DYNAMICS (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the P&L explain"}
+        if int(lag) != lag or lag < 1:
+            return {"success": False, "error": f"lag {lag!r} is not an integer >= 1"}
+        start = time.time()
+        book, error = self._book(frames, book_file)
+        if error:
+            return {"success": False, "error": error}
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_fit = n_bf = n_pairs = n_dead = 0
+        s_actual = s_ss = s_sm = 0.0
+        for res, fit in zip(results, builder.svi(results)):
+            sv = _host_flags(fit.flags)[_host_flags(res.quotes) > 0]
+            n_rows += sv.size
+            n_fit += int(((sv & _lib.SV_DEAD) == 0).sum())
+            n_bf += int(((sv & _lib.SV_BUTTERFLY) != 0).sum())
+            held = book[book["underlying"] == res.underlying].reset_index(drop=True)
+            if held.empty:                                   # no position in this underlying: no table for it
+                print(f"  {res.underlying}: no option of the book, skipped")
+                continue
+            table = explain_frame(builder.explain([res], held, [fit], lag=int(lag)), [res])
+            self.store.write_table(EXPLAIN_TABLE, res.underlying, table)
+            live = table[np.isfinite(table["actual"].to_numpy(np.float64))]
+            s_actual += float(live["actual"].abs().sum())
+            s_ss += float(live["resid_ss"].abs().sum())
+            s_sm += float(live["resid_sm"].abs().sum())
+            dead = int(table["n_dead"].sum())
+            n_pairs += len(table)
+            n_dead += dead
+            print(f"  {res.underlying}: {len(held)} options, {len(table)} pairs, {dead} dead option marks")
+        duration = time.time() - start
+        un_ss, un_sm = (s_ss / s_actual, s_sm / s_actual) if s_actual > 0 else (float("nan"), float("nan"))
+        print(f"\nEXPLAIN COMPLETE: {duration:.1f}s, underlyings {len(results)}, pairs {n_pairs:,}, dead {n_dead:,}, "
+              f"unexplained: sticky strike {un_ss:.3%}, sticky moneyness {un_sm:.3%}")
+        return {"success": n_pairs > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
+                "explain_rows": n_pairs, "dead_options": n_dead, "unexplained_ss": un_ss, "unexplained_sm": un_sm, "duration": duration}
 
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
@@ -569,8 +631,9 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "all"], default="all")
-    parser.add_argument("--book", metavar="FILE", help="--task risk: a CSV of symbol, quantity (default: every listed contract, +1 each)")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "all"], default="all")
+    parser.add_argument("--book", metavar="FILE", help="--task risk / explain: a CSV of symbol, quantity (default: every listed contract, +1 each)")
+    parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain: the pair is snapshot p and snapshot p + N (default 1)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -626,6 +689,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_ssvi()
             elif args.task == "risk":
                 result = pipeline.run_risk(args.book)
+            elif args.task == "explain":
+                result = pipeline.run_explain(args.book, args.lag)
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -745,6 +745,57 @@ typedef struct ivs_book_args {
 int ivs_svi_book_f64(const ivs_book_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * P&L explain of a book between snapshots (rules X0-X9; additive to ABI 5).  Inputs as for
+ * ivs_svi_book_f64 without the shocks, plus lag >= 1.  Pair p = 0 .. P-1, P = max(B - lag, 0), has end 0 = snapshot p and end 1 =
+ * snapshot p + lag.  The contract is end 0's: K = spot[p] u[p][q] (strike_mode 0) or u[p][q] (1), used as an absolute strike at
+ * end 1, whose u is not read; tau0 = tau[p][q], tau1 = tau[p+lag][q] (the same list with q_stride 0), dS = S1 - S0,
+ * dt = tau0 - tau1.  Three placements by the rules of ivs_svi_eval_f64: (a) end 0 at (S0, K, tau0) with every Greek of
+ * ivs_svi_greeks_f64 and the price P0, (b) end 1 at (S1, K, tau1) with the price P1 and the vol sigma1 = sqrt(W / tau1), (c) end
+ * 0's slices at tau1, read at x = log(K/S0) - rate tau1 (sigma0_ss) and at x = log(K/S1) - rate tau1 (sigma0_sm).
+ *
+ * Per option, each [P][Q] and each may be NULL (then not written):
+ *   actual                             P1 - P0
+ *   theta_pnl                          theta dt
+ *   delta_ss, gamma_ss, vega_ss        delta_ss dS, (gamma_ss / 2) dS^2, vega (sigma1 - sigma0_ss)
+ *   resid_ss                           actual - (((theta_pnl + delta_ss) + gamma_ss) + vega_ss), in that order
+ *   delta_sm, gamma_sm, vega_sm        the same from the sticky-moneyness Greeks and sigma0_sm
+ *   resid_sm                           likewise
+ * A product that is a zero of either sign is written as +0.0.
+ *   flags [P][Q] (int32)               the IVS_SE_* bits of placement (a) in bits 0-7 (NEG_FWD included), of (b) in bits 8-15, of
+ *                                      (c) in bits 16-23; required
+ *   net [P][12]                        sum over the live options of qty x the ten figures above, in that order, then of
+ *                                      qty P0 and of |qty| P0; required
+ *   n_dead [P] (int32)                 required
+ * An option is dead in a pair when any placement is dead or its quantity is not finite: NaN in its ten figures, nothing added to
+ * net.  A pair with an UNORDERED end or an end without a live slice has NaN in every net entry and n_dead = Q.  The sums are
+ * formed as in ivs_svi_book_f64 (no atomics, an order that depends on Q alone): the bits of a pair do not depend on B, on lag or on
+ * the other pairs of the call.  A pair whose two ends carry the same bits in params, Tq, spot and tau has exactly +0.0 in the ten
+ * figures of every live option and in net[0..9].
+ *
+ * IVS_EINVAL: null args or a null required pointer, a negative size, a stride that is neither 0 nor the full size, a
+ * strike_mode that is not 0 or 1; IVS_ERANGE: mT > 64, lag < 1, B*mT or B*Q >= 2^31 (so P*Q < 2^31).  B <= lag, mT == 0 or Q == 0
+ * is a no-op (nothing is written; engine.svi_explain defines the result); the limits above are checked before that.  A refused
+ * call launches nothing.  No workspace, no allocation, no synchronisation (capturable); ONE launch.
+ */
+typedef struct ivs_explain_args {
+    const double* params; /* [B][mT][5] */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* u; const double* tau; int64_t q_stride;
+    const uint8_t* is_put; /* [Q] or NULL */
+    const double* qty;     /* [Q] */
+    int32_t strike_mode;
+    int32_t mT; int64_t Q; int64_t B;
+    int32_t lag;
+    double* actual; double* theta_pnl; double* delta_ss; double* gamma_ss; double* vega_ss; double* resid_ss;
+    double* delta_sm; double* gamma_sm; double* vega_sm; double* resid_sm; /* [P][Q], each may be NULL */
+    double* net;       /* [P][12] */
+    int32_t* n_dead;   /* [P] */
+    int32_t* flags;    /* [P][Q] */
+} ivs_explain_args;
+int ivs_svi_explain_f64(const ivs_explain_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.

@@ -182,6 +182,16 @@ class BookArgs(C.Structure):
                 ("net", _p), ("n_dead", _p), ("pnl_ss", _p), ("pnl_sm", _p), ("cell_flags", _p), ("cells_per_wg", _i32)]
 
 
+class ExplainArgs(C.Structure):
+    """ivs_explain_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("u", _p), ("tau", _p), ("q_stride", _i64), ("is_put", _p), ("qty", _p), ("strike_mode", _i32), ("mT", _i32),
+                ("Q", _i64), ("B", _i64), ("lag", _i32),
+                ("actual", _p), ("theta_pnl", _p), ("delta_ss", _p), ("gamma_ss", _p), ("vega_ss", _p), ("resid_ss", _p),
+                ("delta_sm", _p), ("gamma_sm", _p), ("vega_sm", _p), ("resid_sm", _p),
+                ("net", _p), ("n_dead", _p), ("flags", _p)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -230,6 +240,7 @@ SIGNATURES = {
     "ivs_svi_eval_f64": (C.c_int, [C.POINTER(EvalArgs), _p, _sz, _p]),
     "ivs_svi_greeks_f64": (C.c_int, [C.POINTER(GreeksArgs), _p, _sz, _p]),
     "ivs_svi_book_f64": (C.c_int, [C.POINTER(BookArgs), _p, _sz, _p]),
+    "ivs_svi_explain_f64": (C.c_int, [C.POINTER(ExplainArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

@@ -14,6 +14,7 @@
 #include "ivs_distribution.hpp"
 #include "ivs_svi_surface.hpp"
 #include "ivs_risk.hpp"
+#include "ivs_explain.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
 #include "ivs_implied.hpp"
@@ -111,7 +112,7 @@ int32_t rows_per_wave(int64_t rows, int cap, int forced) {
     return (int32_t)(forced > 0 ? forced : group);
 }
 
-// ivs_svi_eval_f64, ivs_svi_greeks_f64, ivs_svi_book_f64: the shape of B snapshots of mT slices and Q queries / options each
+// ivs_svi_eval_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64: the shape of B snapshots of mT slices and Q queries / options each
 int check_query_shape(const char* fn, int64_t B, int32_t mT, int64_t Q, int64_t tq_stride, int64_t q_stride, int32_t strike_mode) {
     if (B < 0 || mT < 0 || Q < 0 || tq_stride < 0 || q_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
     if (strike_mode != 0 && strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, strike_mode);
@@ -707,6 +708,27 @@ int ivs_svi_book_f64(const ivs_book_args* a, void*, size_t, void* stream) {
     const int64_t grid = a->B * nchunk;                     // <= B * max(ncell, 1) < 2^31
     hipLaunchKernelGGL(ivs::svi_book_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
     return end_call("svi_book_kernel");
+}
+
+int ivs_svi_explain_f64(const ivs_explain_args* a, void*, size_t, void* stream) {
+    const char* fn = "ivs_svi_explain_f64";
+    if (int rc = begin_call(fn, a)) return rc;
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->Q, a->tq_stride, a->q_stride, a->strike_mode)) return rc;
+    if (a->lag < 1) return fail(IVS_ERANGE, "%s: lag=%d < 1", fn, a->lag);
+    if (a->B <= a->lag || a->mT == 0 || a->Q == 0) return IVS_OK;                                  // X9
+    if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->qty || !a->net || !a->n_dead || !a->flags)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (int rc = check_query_launch(fn, "options", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
+    ivs::ExplainParams p{};
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put; p.qty = a->qty;
+    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
+    p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.Q = a->Q;
+    p.out[0] = a->actual; p.out[1] = a->theta_pnl; p.out[2] = a->delta_ss; p.out[3] = a->gamma_ss; p.out[4] = a->vega_ss;
+    p.out[5] = a->resid_ss; p.out[6] = a->delta_sm; p.out[7] = a->gamma_sm; p.out[8] = a->vega_sm; p.out[9] = a->resid_sm;
+    p.net = a->net; p.n_dead = a->n_dead; p.flags = a->flags;
+    const int64_t pairs = a->B - a->lag;                    // one workgroup each; P * Q <= B * Q < 2^31
+    hipLaunchKernelGGL(ivs::svi_explain_kernel, dim3((unsigned)pairs), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
+    return end_call("svi_explain_kernel");
 }
 
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void*, size_t, void* stream) {

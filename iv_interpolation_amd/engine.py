@@ -686,6 +686,55 @@ def svi_book(params, Tq, spot, rate, u, tau, qty, spot_shocks=DEFAULT_SPOT_SHOCK
     return {k: out[k] for k in shapes}
 
 
+EXPLAIN_OUTPUTS = ("actual", "theta_pnl", "delta_ss", "gamma_ss", "vega_ss", "resid_ss", "delta_sm", "gamma_sm", "vega_sm", "resid_sm")
+EXPLAIN_NET_COLUMNS = EXPLAIN_OUTPUTS + ("value", "gross")    # the twelve slots of an explain's `net`
+
+
+def svi_explain(params, Tq, spot, rate, u, tau, qty, *, lag: int = 1, is_put=None, strike_mode: int = 0, want=EXPLAIN_OUTPUTS,
+                out=None, stream=None):
+    """P&L explain of a book of options between snapshot p and snapshot p + lag (ivs_svi_explain_f64; rules X0-X9 of
+    DESIGN.md section 18): the realised change of every option's price split into theta, delta, gamma, vega and a remainder
+    under sticky strike and under sticky moneyness, and the same summed over the book.  Inputs as in svi_book without the
+    shocks; lag >= 1 (ValueError otherwise).  There are P = max(B - lag, 0) pairs; the contract (strike, side, quantity) is
+    the one of the pair's first snapshot.
+    want: which of EXPLAIN_OUTPUTS to write; one left out is None in the result.
+    `out`: optional dict of preallocated outputs (float64 [P,Q] per value, flags int32 [P,Q], net float64 [P,12], n_dead int32
+    [P]).
+    The C call writes nothing when mT == 0 or Q == 0; the wrapper then fills the result itself as svi_book does: without a
+    slice every pair is degenerate (NaN, n_dead = Q, every placement DEAD), and a book without options has 0 in every sum and
+    count.
+    Returns dict(the ten values, flags, net, n_dead) of device tensors; net's columns are EXPLAIN_NET_COLUMNS, the flags the
+    _lib.SE_* bits of the three placements in bits 0-7, 8-15 and 16-23."""
+    if strike_mode not in (0, 1):
+        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    if int(lag) != lag or lag < 1:
+        raise ValueError(f"lag {lag!r} is not an integer >= 1")
+    want = _wanted(want, EXPLAIN_OUTPUTS)
+    torch = require_device()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
+    P = max(B - int(lag), 0)
+    shapes = {k: ((P, Q), torch.float64, k in want) for k in EXPLAIN_OUTPUTS}
+    shapes.update(flags=((P, Q), torch.int32, True), net=((P, 12), torch.float64, True), n_dead=((P,), torch.int32, True))
+    out = _outputs(torch, out, shapes, params.device)
+    a = _slice_fields(_lib.ExplainArgs(), params, Tq, spot, rate)
+    _query_fields(a, u, tau, strike_mode)
+    a.is_put, a.qty, a.lag = _ptr(is_put), _ptr(qty), int(lag)
+    for k in shapes:
+        setattr(a, k, _ptr(out[k]))
+    _call(torch, "ivs_svi_explain_f64", a, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
+    if P > 0 and (mT == 0 or Q == 0):                        # the C call is a no-op: the result is defined here
+        empty = float("nan") if mT == 0 else 0.0             # X2: no live slice -> NaN and n_dead = Q; a book without options is worth 0
+        dead = _lib.SE_DEAD | _lib.SE_DEAD << 8 | _lib.SE_DEAD << 16
+        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+            out["net"].fill_(empty)
+            out["n_dead"].fill_(Q if mT == 0 else 0)
+            out["flags"].fill_(dead)
+            for k in want:
+                out[k].fill_(float("nan"))
+    return {k: out[k] for k in shapes}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

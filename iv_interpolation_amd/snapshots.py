@@ -234,6 +234,30 @@ class RiskReport:
     cell_flags: object               # [B, nA, nV] int32, IVS_SB_*
 
 
+EXPLAIN_COLUMNS = ("actual", "theta_pnl", "delta_ss", "gamma_ss", "vega_ss", "resid_ss", "delta_sm", "gamma_sm", "vega_sm", "resid_sm")
+EXPLAIN_NET_COLUMNS = EXPLAIN_COLUMNS + ("value", "gross")
+
+
+@dataclass
+class ExplainReport:
+    """One underlying's book of options with the P&L of every pair of snapshots (p, p + lag) explained (rules X0-X9).  The
+    value arrays are device tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    start: pd.DatetimeIndex          # [P] the pair's first snapshot
+    end: pd.DatetimeIndex            # [P] its second
+    lag: int
+    strikes: np.ndarray              # [Q]
+    expiries: pd.DatetimeIndex       # [Q]
+    is_put: np.ndarray               # [Q] bool
+    quantity: np.ndarray             # [Q]
+    tau: np.ndarray                  # [B, Q] years from the snapshot to the expiry
+    rate: float
+    values: dict                     # the ten figures of EXPLAIN_COLUMNS, each [P, Q]
+    net: object                      # [P, 12] sums of quantity x the ten figures, then of quantity x P0 and |quantity| x P0
+    n_dead: object                   # [P] int32
+    flags: object                    # [P, Q] int32: IVS_SE_* of the placements (a), (b), (c) in bits 0-7, 8-15, 16-23
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -298,6 +322,11 @@ class HipBackend:
         d = lambda a: self._up(a, np.float64)  # noqa: E731
         return engine.svi_book(params, d(Tq), spot, rate, d(u), d(tau), d(qty), spot_shocks, vol_shocks,
                                is_put=self._up(is_put, np.uint8), strike_mode=strike_mode, stream=self.stream)
+
+    def explain(self, params, Tq, spot, rate, u, tau, qty, lag, is_put, strike_mode):
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
+        return engine.svi_explain(params, d(Tq), spot, rate, d(u), d(tau), d(qty), lag=lag, is_put=self._up(is_put, np.uint8),
+                                  strike_mode=strike_mode, stream=self.stream)
 
 
 def _host(a):
@@ -612,6 +641,38 @@ class SnapshotSurfaceBuilder:
             k = be.book(v.params, r.tenors, r.spot, float(rate), u, tau, qty, sa, sv, is_put, 1)
             reports.append(RiskReport(r.underlying, r.dates, strikes, expiry, is_put, qty, tau, float(rate), np.asarray(sa), np.asarray(sv),
                                       dict(g), k["net"], k["n_dead"], k["pnl_ss"], k["pnl_sm"], k["cell_flags"]))
+        return reports
+
+    # ------------------------------------------------------------------ explain
+    def explain(self, results: Sequence[SnapshotSurfaces], book: pd.DataFrame, svi_reports=None, rate: float = 0.0, lag: int = 1,
+                rounds: int = 0) -> List["ExplainReport"]:
+        """The P&L of a book of options between snapshot p and snapshot p + lag of every surface of `results`, explained (rules
+        X0-X9): one ExplainReport per underlying with the realised change of every option's price split into theta, delta,
+        gamma, vega and a remainder under sticky strike and under sticky moneyness, and the book's sums.  book: risk()'s
+        frame.  lag: an integer >= 1; an underlying with lag or fewer snapshots has no pair.  svi_reports as for calendar()."""
+        for c in ("strike", "expiry", "callput", "quantity"):
+            if c not in book.columns:
+                raise KeyError(c)
+        if int(lag) != lag or lag < 1:
+            raise ValueError(f"lag {lag!r} is not an integer >= 1")
+        lag = int(lag)
+        side = book["callput"].astype(str).str.lower().str[:1]
+        if not side.isin(["c", "p"]).all():
+            raise ValueError("callput must start with c or p")
+        is_put = (side == "p").to_numpy(bool)
+        svi_reports = self._slices(results, svi_reports, rate, rounds)
+        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
+        qty = pd.to_numeric(book["quantity"], errors="coerce").to_numpy(np.float64)
+        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v in zip(results, svi_reports):
+            tau = self._tau(expiry, r.dates)
+            u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
+            x = be.explain(v.params, r.tenors, r.spot, float(rate), u, tau, qty, lag, is_put, 1)
+            P = max(len(r.dates) - lag, 0)
+            reports.append(ExplainReport(r.underlying, r.dates[:P], r.dates[len(r.dates) - P:], lag, strikes, expiry, is_put, qty, tau,
+                                         float(rate), {k: x[k] for k in EXPLAIN_COLUMNS}, x["net"], x["n_dead"], x["flags"]))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -1066,3 +1127,59 @@ def greeks_frame(reports: Sequence[RiskReport], snapshots: Sequence[SnapshotSurf
                              "quantity": f64, "tau": f64, **{k: f64 for k in GREEK_COLUMNS}, "flags": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def _explain_pairs(p: ExplainReport, r: SnapshotSurfaces) -> np.ndarray:
+    """The pairs of `p` whose two snapshots both have quotes > 0."""
+    q = _host(r.quotes) > 0
+    P = len(p.start)
+    return np.flatnonzero(q[:P] & q[len(q) - P:]) if P else np.zeros(0, np.int64)
+
+
+def explain_frame(reports: Sequence[ExplainReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per pair of snapshots that both have quotes > 0, ordered by (underlying, start): columns underlying, start, end,
+    dS, the book's net actual, theta_pnl, delta_ss, gamma_ss, vega_ss, resid_ss, delta_sm, gamma_sm, vega_sm, resid_sm, its
+    value and gross value at the start, and n_dead."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = _explain_pairs(p, r)
+        spot = _host(r.spot)
+        net = _host(p.net)[keep]
+        cols = {"underlying": p.underlying, "start": p.start[keep], "end": p.end[keep], "dS": spot[keep + p.lag] - spot[keep]}
+        for n, k in enumerate(EXPLAIN_NET_COLUMNS):
+            cols[k] = net[:, n]
+        cols["n_dead"] = _host(p.n_dead)[keep].astype(np.int32)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64, ns = pd.Series(dtype=np.float64), pd.Series(dtype="datetime64[ns]")
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "start": ns, "end": ns, "dS": f64,
+                             **{k: f64 for k in EXPLAIN_NET_COLUMNS}, "n_dead": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "start"], kind="stable").reset_index(drop=True)
+
+
+def explain_options_frame(reports: Sequence[ExplainReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per (pair of snapshots that both have quotes > 0, option of the book), ordered by (underlying, start) with the
+    options in the book's order: columns underlying, start, end, dS, strike, expiry, callput, quantity, tau_start, tau_end, the
+    ten figures and flags."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = _explain_pairs(p, r)
+        spot = _host(r.spot)
+        n, Q = len(keep), len(p.strikes)
+        cols = {"underlying": p.underlying, "start": p.start[keep].repeat(Q), "end": p.end[keep].repeat(Q),
+                "dS": np.repeat(spot[keep + p.lag] - spot[keep], Q),
+                "strike": np.tile(p.strikes, n), "expiry": p.expiries[np.tile(np.arange(Q), n)],
+                "callput": np.tile(np.where(p.is_put, "p", "c").astype(object), n), "quantity": np.tile(p.quantity, n),
+                "tau_start": p.tau[keep].reshape(-1), "tau_end": p.tau[keep + p.lag].reshape(-1)}
+        for k in EXPLAIN_COLUMNS:
+            cols[k] = _host(p.values[k])[keep].reshape(-1)
+        cols["flags"] = _host(p.flags)[keep].reshape(-1).astype(np.int32)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64, ns = pd.Series(dtype=np.float64), pd.Series(dtype="datetime64[ns]")
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "start": ns, "end": ns, "dS": f64, "strike": f64, "expiry": ns,
+                             "callput": pd.Series(dtype=object), "quantity": f64, "tau_start": f64, "tau_end": f64,
+                             **{k: f64 for k in EXPLAIN_COLUMNS}, "flags": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "start"], kind="stable").reset_index(drop=True)
