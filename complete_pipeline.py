@@ -37,6 +37,7 @@ SSVI_TABLE = "iv_ssvi"
 IMPLIED_TABLE = "iv_implied"
 RISK_TABLE = "iv_risk"
 EXPLAIN_TABLE = "iv_explain"
+VAR_TABLE = "iv_var"
 SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
@@ -451,6 +452,66 @@ class CompleteOptimizedPipeline:
         return {"success": n_pairs > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "explain_rows": n_pairs, "dead_options": n_dead, "unexplained_ss": un_ss, "unexplained_sm": un_sm, "duration": duration}
 
+    def run_var(self, book_file: Optional[str] = None, lag: int = 1, window: int = 256, levels=(0.05, 0.01), min_scenarios: int = 20) -> dict:
+        """Historical-simulation VaR and expected shortfall: the snapshots of run_surfaces and the slices
+        of run_svi, then, per snapshot, the book revalued on the surface under each of the last `window` moves the chain made
+        over `lag` snapshots, and the tail of that P&L distribution at the tail probabilities `levels`, on the device (NaN for a
+        snapshot with fewer than `min_scenarios` valid scenarios).  The book
+        is run_risk's.  One `iv_var` table per underlying (var_frame's columns).  Besides run_svi's keys the result has var_rows,
+        dead_options and `backtest`: per level a dict(tp, eligible, exceedances, exceedance_rate): eligible = the snapshots with a
+        finite VaR whose pair p -> p + lag has a finite net actual P&L in the P&L explain, exceedances = those whose actual P&L is
+        below -VaR, exceedance_rate = their share (NaN without an eligible snapshot), to be read beside tp."""
+        from iv_interpolation_amd import _lib
+        from iv_interpolation_amd.engine import hsim_settings
+        from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, explain_frame, var_frame
+        print("\nVAR: HISTORICAL-SIMULATION VAR AND EXPECTED SHORTFALL OF A BOOK (MI355X engine)")
+        print("-" * 40)
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the VaR"}
+        try:
+            lag, window, levels, min_scenarios, _ = hsim_settings(lag, window, levels, min_scenarios)
+        except (ValueError, TypeError) as e:
+            return {"success": False, "error": str(e)}
+        start = time.time()
+        book, error = self._book(frames, book_file)
+        if error:
+            return {"success": False, "error": error}
+        builder = SnapshotSurfaceBuilder(backend=self._surface_backend)
+        results = builder.build(frames)
+        n_rows = n_fit = n_bf = n_var = n_dead = 0
+        eligible, exceed = [0] * len(levels), [0] * len(levels)
+        for res, fit in zip(results, builder.svi(results)):
+            sv = _host_flags(fit.flags)[_host_flags(res.quotes) > 0]
+            n_rows += sv.size
+            n_fit += int(((sv & _lib.SV_DEAD) == 0).sum())
+            n_bf += int(((sv & _lib.SV_BUTTERFLY) != 0).sum())
+            held = book[book["underlying"] == res.underlying].reset_index(drop=True)
+            if held.empty:                                   # no position in this underlying: no table for it
+                print(f"  {res.underlying}: no option of the book, skipped")
+                continue
+            table = var_frame(builder.var([res], held, [fit], lag=lag, window=window, tail_probs=levels, min_scenarios=min_scenarios), [res])
+            self.store.write_table(VAR_TABLE, res.underlying, table)
+            realised = explain_frame(builder.explain([res], held, [fit], lag=lag), [res])
+            both = table.merge(realised[["start", "actual"]], left_on="date", right_on="start", how="inner")
+            actual = both["actual"].to_numpy(np.float64)
+            for n, tp in enumerate(levels):
+                var = both[f"var_{tp:g}"].to_numpy(np.float64)
+                ok = np.isfinite(var) & np.isfinite(actual)
+                eligible[n] += int(ok.sum())
+                exceed[n] += int((ok & (actual < -var)).sum())
+            dead = int(table["n_dead"].sum())
+            n_var += len(table)
+            n_dead += dead
+            print(f"  {res.underlying}: {len(held)} options, {len(table)} snapshots, {dead} dead option marks")
+        duration = time.time() - start
+        backtest = [{"tp": tp, "eligible": e, "exceedances": x, "exceedance_rate": x / e if e else float("nan")}
+                    for tp, e, x in zip(levels, eligible, exceed)]
+        print(f"\nVAR COMPLETE: {duration:.1f}s, underlyings {len(results)}, snapshots {n_var:,}, dead {n_dead:,}, back-test: "
+              + ", ".join(f"tp {b['tp']:g}: {b['exceedances']}/{b['eligible']} ({b['exceedance_rate']:.3%})" for b in backtest))
+        return {"success": n_var > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
+                "var_rows": n_var, "dead_options": n_dead, "backtest": backtest, "duration": duration}
+
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
         quantiles, level probabilities and tails of every tenor row on the device, and one `iv_distribution` table per
@@ -631,9 +692,12 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "all"], default="all")
-    parser.add_argument("--book", metavar="FILE", help="--task risk / explain: a CSV of symbol, quantity (default: every listed contract, +1 each)")
-    parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain: the pair is snapshot p and snapshot p + N (default 1)")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "all"], default="all")
+    parser.add_argument("--book", metavar="FILE", help="--task risk / explain / var: a CSV of symbol, quantity (default: every listed contract, +1 each)")
+    parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain / var: the pair is snapshot p and snapshot p + N (default 1)")
+    parser.add_argument("--window", type=int, default=256, metavar="W", help="--task var: scenarios kept per snapshot (default 256)")
+    parser.add_argument("--levels", default="0.05,0.01", metavar="P,P", help="--task var: tail probabilities (default 0.05,0.01)")
+    parser.add_argument("--min-scenarios", type=int, default=20, metavar="N", help="--task var: fewer valid scenarios than N give no VaR (default 20)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -691,6 +755,8 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_risk(args.book)
             elif args.task == "explain":
                 result = pipeline.run_explain(args.book, args.lag)
+            elif args.task == "var":
+                result = pipeline.run_var(args.book, args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios)
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

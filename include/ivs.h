@@ -796,6 +796,68 @@ typedef struct ivs_explain_args {
 int ivs_svi_explain_f64(const ivs_explain_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Historical-simulation value-at-risk and expected shortfall of a book per snapshot (rules H0-H9; additive
+ * to ABI 5).  Inputs as for ivs_svi_explain_f64, plus window (scenarios kept per snapshot), nL tail probabilities (host array),
+ * min_scen and scen_per_wg.  For snapshot p, scenario s = 0 .. window-1 is the past pair with start j = p - lag - s and end
+ * j + lag; it exists while j >= 0.  The scenario moves today's spot by the pair's quotient, S' = S_p (S_{j+lag} / S_j), and every
+ * live option's vol by the pair's change at the option's new moneyness x' = log(K / S') - rate tau and today's tau:
+ * sigma' = sigma_p(x') + (sigma_{j+lag}(x') - sigma_j(x')), each sigma = sqrt(W(x') / tau) with that snapshot's own bracket and
+ * weight by the rules of ivs_svi_eval_f64.  P' is the price formula of ivs_svi_greeks_f64 at (S', x', sigma' sqrt(tau)); the base
+ * price P is the same code with the quotient 1.0 and the change +0.0.
+ *   pnl [B][window]                    sum over the live options of qty (P' - P), formed as in ivs_svi_book_f64 (no atomics, an
+ *                                      order that depends on Q alone): the bits of a scenario depend on snapshot p, the pair's two
+ *                                      snapshots and the book alone.  NaN when the scenario has a flag.  Exactly +0.0 for a pair
+ *                                      whose two ends carry the same bits in params, Tq and spot.  Required.
+ *   scen_flags [B][window] (int32)     IVS_HS_ABSENT: j < 0; IVS_HS_VOID_PAIR: an end of the pair, or snapshot p itself, is
+ *                                      UNORDERED or has no live slice (a spot that is not finite and > 0 leaves none); either
+ *                                      is the scenario's only bit.  IVS_HS_NEG_VOL: a live option has !(sigma' > 0).  Required.
+ *   n_valid [B] (int32)                the ranked scenarios: no flag and a P&L that is a number.  Required.
+ *   var, es [B][nL]                    with n = n_valid, m = max(1, floor(n tp)) (one IEEE product): var = 0.0 - (the m-th smallest
+ *                                      P&L), es = 0.0 - (the sum of the m smallest, added in rank order from +0.0, divided by m); ties
+ *                                      rank by the lower s.  NaN when n < min_scen.  Required when nL > 0.
+ *   worst [B] (int32)                  the s of the smallest P&L, -1 without a ranked scenario.  Required.
+ *   n_dead [B] (int32)                 as in ivs_svi_book_f64.  Required.
+ *   value [B][2]                       sum of qty P0 and of |qty| P0 over the live options, P0 the price of ivs_svi_greeks_f64;
+ *                                      may be NULL.  NaN for an UNORDERED snapshot or one without a live slice (n_dead = Q).
+ * scen_per_wg: how many scenarios one workgroup takes; 0 lets the call choose, 1..window forces it (the same bits).  stages: 0 =
+ * both launches, 1 = the P&L kernel alone, 2 = the order statistics alone, read from pnl and scen_flags as given (measuring).
+ *
+ * IVS_EINVAL: null args or a null required pointer, a negative size, a stride that is neither 0 nor the full size, a
+ * strike_mode that is not 0 or 1; IVS_ERANGE: mT > 64, lag < 1, window outside 1..1024, nL outside 0..8, a tail probability that
+ * is not finite or not inside (0, 1), min_scen < 1, scen_per_wg outside 0..window, stages outside 0..2, B*mT, B*Q or B*window >=
+ * 2^31.  B == 0, mT == 0 or Q == 0 is a no-op (nothing is written; engine.svi_hsim defines the result); the limits above are
+ * checked before that.  B <= lag is not empty: every scenario is ABSENT.  A refused call launches nothing.  No workspace, no
+ * allocation, no synchronisation (capturable); TWO launches.
+ */
+enum {
+    IVS_HS_ABSENT = 1,
+    IVS_HS_VOID_PAIR = 2,
+    IVS_HS_NEG_VOL = 4
+};
+typedef struct ivs_hsim_args {
+    const double* params; /* [B][mT][5] */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* u; const double* tau; int64_t q_stride;
+    const uint8_t* is_put; /* [Q] or NULL */
+    const double* qty;     /* [Q] */
+    int32_t strike_mode;
+    int32_t mT; int64_t Q; int64_t B;
+    int32_t lag;
+    int32_t window;            /* 1..1024 */
+    const double* tail_probs;  /* host */ int32_t nL; /* 0..8 */
+    int32_t min_scen;          /* >= 1 */
+    int32_t scen_per_wg;       /* 0 = chosen by the call; 1..window = tuning / testing override, same bits */
+    int32_t stages;            /* 0 = both; 1 = P&L only; 2 = order statistics only */
+    double* pnl;           /* [B][window] */
+    int32_t* scen_flags;   /* [B][window] */
+    double* var; double* es; /* [B][nL] */
+    int32_t* n_valid; int32_t* n_dead; int32_t* worst; /* [B] */
+    double* value;         /* [B][2], may be NULL */
+} ivs_hsim_args;
+int ivs_svi_hsim_f64(const ivs_hsim_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.

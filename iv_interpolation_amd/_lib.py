@@ -32,6 +32,9 @@ ST_MAX_TENORS, SC_MAX_ROWS_PER_WAVE = 64, 32
 # IVS_SB_*: per-cell flags of the scenario grid of a book, one bit per dynamic
 SB_NEG_VOL_SS, SB_NEG_VOL_SM = 1, 2
 RK_MAX_SHOCKS, RK_MAX_GRID = 64, 1024
+# IVS_HS_*: per-scenario flags of the historical simulation
+HS_ABSENT, HS_VOID_PAIR, HS_NEG_VOL = 1, 2, 4
+HS_MAX_WINDOW, HS_MAX_LEVELS = 1024, 8
 # IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
@@ -192,6 +195,16 @@ class ExplainArgs(C.Structure):
                 ("net", _p), ("n_dead", _p), ("flags", _p)]
 
 
+class HsimArgs(C.Structure):
+    """ivs_hsim_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("u", _p), ("tau", _p), ("q_stride", _i64), ("is_put", _p), ("qty", _p), ("strike_mode", _i32), ("mT", _i32),
+                ("Q", _i64), ("B", _i64), ("lag", _i32), ("window", _i32),
+                ("tail_probs", C.POINTER(C.c_double)), ("nL", _i32), ("min_scen", _i32), ("scen_per_wg", _i32), ("stages", _i32),
+                ("pnl", _p), ("scen_flags", _p), ("var", _p), ("es", _p), ("n_valid", _p), ("n_dead", _p), ("worst", _p),
+                ("value", _p)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -241,6 +254,7 @@ SIGNATURES = {
     "ivs_svi_greeks_f64": (C.c_int, [C.POINTER(GreeksArgs), _p, _sz, _p]),
     "ivs_svi_book_f64": (C.c_int, [C.POINTER(BookArgs), _p, _sz, _p]),
     "ivs_svi_explain_f64": (C.c_int, [C.POINTER(ExplainArgs), _p, _sz, _p]),
+    "ivs_svi_hsim_f64": (C.c_int, [C.POINTER(HsimArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

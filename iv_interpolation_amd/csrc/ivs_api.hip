@@ -15,6 +15,7 @@
 #include "ivs_svi_surface.hpp"
 #include "ivs_risk.hpp"
 #include "ivs_explain.hpp"
+#include "ivs_hsim.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
 #include "ivs_implied.hpp"
@@ -729,6 +730,64 @@ int ivs_svi_explain_f64(const ivs_explain_args* a, void*, size_t, void* stream) 
     const int64_t pairs = a->B - a->lag;                    // one workgroup each; P * Q <= B * Q < 2^31
     hipLaunchKernelGGL(ivs::svi_explain_kernel, dim3((unsigned)pairs), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
     return end_call("svi_explain_kernel");
+}
+
+int ivs_svi_hsim_f64(const ivs_hsim_args* a, void*, size_t, void* stream) {
+    const char* fn = "ivs_svi_hsim_f64";
+    if (int rc = begin_call(fn, a)) return rc;
+    if (a->nL < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->Q, a->tq_stride, a->q_stride, a->strike_mode)) return rc;
+    if (a->lag < 1) return fail(IVS_ERANGE, "%s: lag=%d < 1", fn, a->lag);
+    if (a->window < 1 || a->window > ivs::HS_MAX_WINDOW)
+        return fail(IVS_ERANGE, "%s: window=%d outside [1,%d]", fn, a->window, ivs::HS_MAX_WINDOW);
+    if (a->nL > ivs::HS_MAX_LEVELS) return fail(IVS_ERANGE, "%s: nL=%d > %d tail probabilities", fn, a->nL, ivs::HS_MAX_LEVELS);
+    if (a->nL > 0 && !a->tail_probs) return fail(IVS_EINVAL, "%s: null tail probabilities", fn);
+    for (int l = 0; l < a->nL; ++l)
+        if (!(a->tail_probs[l] > 0.0 && a->tail_probs[l] < 1.0))
+            return fail(IVS_ERANGE, "%s: tail probability %d (%g) is not inside (0, 1)", fn, l, a->tail_probs[l]);
+    if (a->min_scen < 1) return fail(IVS_ERANGE, "%s: min_scen=%d < 1", fn, a->min_scen);
+    if (a->scen_per_wg < 0 || a->scen_per_wg > a->window)
+        return fail(IVS_ERANGE, "%s: scen_per_wg=%d outside [0,%d]", fn, a->scen_per_wg, a->window);
+    if (a->stages < 0 || a->stages > 2) return fail(IVS_ERANGE, "%s: stages=%d outside [0,2]", fn, a->stages);
+    if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;                                       // H9
+    if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->qty || !a->pnl || !a->scen_flags || !a->n_valid || !a->n_dead ||
+        !a->worst || (a->nL > 0 && (!a->var || !a->es)))
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (int rc = check_query_launch(fn, "options", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
+    if (a->B > 0x7fffffffLL / a->window)
+        return fail(IVS_ERANGE, "%s: %lld x %d scenarios exceed one launch", fn, (long long)a->B, a->window);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (a->stages != 2) {
+        ivs::HsimParams p{};
+        p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put; p.qty = a->qty;
+        p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
+        p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.window = a->window; p.Q = a->Q;
+        p.pnl = a->pnl; p.scen_flags = a->scen_flags; p.value = a->value; p.n_dead = a->n_dead;
+        // scenarios per workgroup: the whole window while the snapshots alone give every CU sixteen workgroups, shorter runs
+        // below that, as ivs_svi_book_f64 spreads its cells.  Sixteen, not its two: a workgroup that takes 256 scenarios of a
+        // 1024-option book runs for milliseconds, and with only five rounds of them per CU the last round stands half empty
+        // (131.0 ms against 126.4 ms with runs of 128 or 64 on the bench of DESIGN.md section 19).  The sums of a scenario do
+        // not depend on the split.
+        int dev, cus;
+        current_device(dev, cus);
+        int64_t need = (16 * (int64_t)cus + a->B - 1) / a->B;
+        need = need < 1 ? 1 : (need > a->window ? a->window : need);
+        int spw = (int)((a->window + need - 1) / need);
+        if (a->scen_per_wg > 0) spw = a->scen_per_wg;           // tuning / testing override
+        p.spw = spw; p.nchunk = (a->window + spw - 1) / spw;
+        const int64_t grid = a->B * p.nchunk;                   // <= B * window < 2^31
+        hipLaunchKernelGGL(ivs::svi_hsim_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, st, p);
+        if (int rc = end_call("svi_hsim_kernel")) return rc;
+    }
+    if (a->stages != 1) {
+        ivs::HsimTailParams t{};
+        t.pnl = a->pnl; t.scen_flags = a->scen_flags; t.window = a->window; t.nL = a->nL; t.min_scen = a->min_scen;
+        for (int l = 0; l < a->nL; ++l) t.tp[l] = a->tail_probs[l];
+        t.var = a->var; t.es = a->es; t.n_valid = a->n_valid; t.worst = a->worst;
+        hipLaunchKernelGGL(ivs::hsim_tail_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, st, t);
+        return end_call("hsim_tail_kernel");
+    }
+    return IVS_OK;
 }
 
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void*, size_t, void* stream) {

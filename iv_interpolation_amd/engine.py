@@ -735,6 +735,85 @@ def svi_explain(params, Tq, spot, rate, u, tau, qty, *, lag: int = 1, is_put=Non
     return {k: out[k] for k in shapes}
 
 
+DEFAULT_TAIL_PROBS = (0.05, 0.01)
+HSIM_OUTPUTS = ("pnl", "scen_flags", "var", "es", "n_valid", "n_dead", "worst", "value")
+
+
+def hsim_settings(lag, window, tail_probs, min_scen, scen_per_wg=0):
+    """The host-side checks of a historical simulation: lag an integer >= 1, window 1..1024, at most 8
+    tail probabilities, each finite and inside (0, 1), min_scen >= 1, scen_per_wg 0..window; ValueError otherwise.  Returns
+    (lag, window, tail_probs as a list, min_scen, scen_per_wg)."""
+    import math
+    for name, v, lo in (("lag", lag, 1), ("window", window, 1), ("min_scen", min_scen, 1), ("scen_per_wg", scen_per_wg, 0)):
+        if int(v) != v or v < lo:
+            raise ValueError(f"{name} {v!r} is not an integer >= {lo}")
+    if window > _lib.HS_MAX_WINDOW:
+        raise ValueError(f"window {window}: at most {_lib.HS_MAX_WINDOW} scenarios per snapshot are supported")
+    if scen_per_wg > window:
+        raise ValueError(f"scen_per_wg {scen_per_wg} exceeds the window {window}")
+    tp = [float(x) for x in tail_probs]
+    if len(tp) > _lib.HS_MAX_LEVELS:
+        raise ValueError(f"{len(tp)} tail probabilities: at most {_lib.HS_MAX_LEVELS} are supported")
+    if any(not (math.isfinite(x) and 0.0 < x < 1.0) for x in tp):
+        raise ValueError(f"tail probabilities must be finite and inside (0, 1), got {tp!r}")
+    return int(lag), int(window), tp, int(min_scen), int(scen_per_wg)
+
+
+def svi_hsim(params, Tq, spot, rate, u, tau, qty, *, lag: int = 1, window: int = 256, tail_probs=DEFAULT_TAIL_PROBS, min_scen: int = 20,
+             is_put=None, strike_mode: int = 0, value: bool = True, out=None, stream=None, scen_per_wg: int = 0, stages: int = 0):
+    """Historical-simulation VaR and expected shortfall of a book of options per snapshot (ivs_svi_hsim_f64; rules H0-H9 of
+    DESIGN.md section 19): for snapshot p, scenario s is the past pair of snapshots (p - lag - s, p - s); it moves today's spot by
+    the pair's quotient and every option's vol by the pair's change at fixed moneyness and tenor, and the book is revalued on
+    the surface.  Inputs as in svi_explain; hsim_settings has the limits of lag, window, tail_probs, min_scen and scen_per_wg.
+    value: whether to form the book's value and gross value [B,2] (None in the result otherwise).
+    `out`: optional dict of preallocated outputs (pnl float64 [B,window], scen_flags int32 [B,window], var / es float64 [B,nL],
+    n_valid / n_dead / worst int32 [B], value float64 [B,2]).
+    scen_per_wg: 0 lets the call choose how many scenarios a workgroup takes; 1..window forces it (the same bits).  stages: 0 =
+    everything, 1 = pnl, scen_flags, value and n_dead alone, 2 = the order statistics alone from out's pnl and scen_flags.
+    The C call writes nothing when mT == 0 or Q == 0; the wrapper then fills the result itself as svi_book does: without a
+    slice every snapshot is degenerate (every existing scenario VOID_PAIR and NaN, n_valid 0, n_dead = Q, NaN in var / es /
+    value), and a book without options has +0.0 in every existing scenario, VaR, ES and value.
+    Returns dict(pnl, scen_flags, var, es, n_valid, n_dead, worst, value) of device tensors; the flags are the _lib.HS_* bits."""
+    if strike_mode not in (0, 1):
+        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    if stages not in (0, 1, 2):
+        raise ValueError(f"stages {stages!r} is not 0, 1 or 2")
+    lag, window, tp, min_scen, scen_per_wg = hsim_settings(lag, window, tail_probs, min_scen, scen_per_wg)
+    torch = require_device()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
+    nL = len(tp)
+    i32, f64 = torch.int32, torch.float64
+    shapes = {"pnl": ((B, window), f64, True), "scen_flags": ((B, window), i32, True), "var": ((B, nL), f64, True),
+              "es": ((B, nL), f64, True), "n_valid": ((B,), i32, True), "n_dead": ((B,), i32, True), "worst": ((B,), i32, True),
+              "value": ((B, 2), f64, bool(value))}
+    out = _outputs(torch, out, shapes, params.device)
+    a = _slice_fields(_lib.HsimArgs(), params, Tq, spot, rate)
+    _query_fields(a, u, tau, strike_mode)
+    a.is_put, a.qty, a.lag, a.window = _ptr(is_put), _ptr(qty), lag, window
+    a.tail_probs, a.nL, a.min_scen, a.scen_per_wg, a.stages = _doubles(tp), nL, min_scen, scen_per_wg, int(stages)
+    for k in shapes:
+        setattr(a, k, _ptr(out[k]))
+    _call(torch, "ivs_svi_hsim_f64", a, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
+    if B > 0 and (mT == 0 or Q == 0):                        # the C call is a no-op: the result is defined here (H9)
+        nan = float("nan")
+        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+            n_p = (torch.arange(B, device=params.device) - lag + 1).clamp(0, window)
+            exists = torch.arange(window, device=params.device)[None, :] < n_p[:, None]
+            here = torch.full((), _lib.HS_VOID_PAIR if mT == 0 else 0, dtype=i32, device=params.device)
+            out["scen_flags"].copy_(torch.where(exists, here, torch.full_like(here, _lib.HS_ABSENT)))
+            out["pnl"].copy_(torch.where(exists & (mT > 0), 0.0, nan))
+            ranked = (n_p >= min_scen) & (mT > 0)
+            for k in ("var", "es"):
+                out[k].copy_(torch.where(ranked[:, None], 0.0, nan).expand(B, nL))
+            out["n_valid"].copy_(n_p if mT > 0 else torch.zeros_like(n_p))
+            out["worst"].copy_(torch.where((n_p > 0) & (mT > 0), 0, -1))
+            out["n_dead"].fill_(Q if mT == 0 else 0)
+            if out["value"] is not None:
+                out["value"].fill_(nan if mT == 0 else 0.0)
+    return {k: out[k] for k in shapes}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

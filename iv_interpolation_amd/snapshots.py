@@ -258,6 +258,32 @@ class ExplainReport:
     flags: object                    # [P, Q] int32: IVS_SE_* of the placements (a), (b), (c) in bits 0-7, 8-15, 16-23
 
 
+@dataclass
+class VarReport:
+    """One underlying's book of options with its historical-simulation VaR and expected shortfall at every snapshot (rules
+    H0-H9).  The value arrays are device tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    lag: int
+    window: int
+    tail_probs: np.ndarray           # [nL]
+    min_scenarios: int
+    strikes: np.ndarray              # [Q]
+    expiries: pd.DatetimeIndex       # [Q]
+    is_put: np.ndarray               # [Q] bool
+    quantity: np.ndarray             # [Q]
+    tau: np.ndarray                  # [B, Q] years from the snapshot to the expiry
+    rate: float
+    pnl: object                      # [B, window] scenario s of snapshot p: the pair (p - lag - s, p - s)
+    scen_flags: object               # [B, window] int32, IVS_HS_*
+    var: object                      # [B, nL] losses are positive
+    es: object                       # [B, nL]
+    n_valid: object                  # [B] int32
+    n_dead: object                   # [B] int32
+    worst: object                    # [B] int32: the scenario of the smallest P&L, -1 without one
+    value: object                    # [B, 2] sums of quantity x price and |quantity| x price
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -327,6 +353,11 @@ class HipBackend:
         d = lambda a: self._up(a, np.float64)  # noqa: E731
         return engine.svi_explain(params, d(Tq), spot, rate, d(u), d(tau), d(qty), lag=lag, is_put=self._up(is_put, np.uint8),
                                   strike_mode=strike_mode, stream=self.stream)
+
+    def hsim(self, params, Tq, spot, rate, u, tau, qty, lag, window, tail_probs, min_scen, is_put, strike_mode):
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
+        return engine.svi_hsim(params, d(Tq), spot, rate, d(u), d(tau), d(qty), lag=lag, window=window, tail_probs=tail_probs,
+                               min_scen=min_scen, is_put=self._up(is_put, np.uint8), strike_mode=strike_mode, stream=self.stream)
 
 
 def _host(a):
@@ -673,6 +704,38 @@ class SnapshotSurfaceBuilder:
             P = max(len(r.dates) - lag, 0)
             reports.append(ExplainReport(r.underlying, r.dates[:P], r.dates[len(r.dates) - P:], lag, strikes, expiry, is_put, qty, tau,
                                          float(rate), {k: x[k] for k in EXPLAIN_COLUMNS}, x["net"], x["n_dead"], x["flags"]))
+        return reports
+
+    # ------------------------------------------------------------------ var
+    def var(self, results: Sequence[SnapshotSurfaces], book: pd.DataFrame, svi_reports=None, rate: float = 0.0, lag: int = 1,
+            window: int = 256, tail_probs=(0.05, 0.01), min_scenarios: int = 20, rounds: int = 0) -> List["VarReport"]:
+        """Historical-simulation VaR and expected shortfall of a book of options at every surface of `results` (rules H0-H9):
+        one VarReport per underlying.  For snapshot p, scenario s is the move the chain made between snapshots p - lag - s and
+        p - s, applied to the book at p with a full revaluation; window: how many of them are kept.  tail_probs: the tail
+        probabilities (0.05 = the 95 % VaR); a snapshot with fewer than min_scenarios valid scenarios has NaN.  book: risk()'s
+        frame.  svi_reports as for calendar()."""
+        from .engine import hsim_settings
+        for c in ("strike", "expiry", "callput", "quantity"):
+            if c not in book.columns:
+                raise KeyError(c)
+        lag, window, tp, min_scenarios, _ = hsim_settings(lag, window, tail_probs, min_scenarios)
+        side = book["callput"].astype(str).str.lower().str[:1]
+        if not side.isin(["c", "p"]).all():
+            raise ValueError("callput must start with c or p")
+        is_put = (side == "p").to_numpy(bool)
+        svi_reports = self._slices(results, svi_reports, rate, rounds)
+        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
+        qty = pd.to_numeric(book["quantity"], errors="coerce").to_numpy(np.float64)
+        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v in zip(results, svi_reports):
+            tau = self._tau(expiry, r.dates)
+            u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
+            h = be.hsim(v.params, r.tenors, r.spot, float(rate), u, tau, qty, lag, window, tp, min_scenarios, is_put, 1)
+            reports.append(VarReport(r.underlying, r.dates, lag, window, np.asarray(tp, np.float64), min_scenarios, strikes, expiry, is_put,
+                                     qty, tau, float(rate), h["pnl"], h["scen_flags"], h["var"], h["es"], h["n_valid"], h["n_dead"],
+                                     h["worst"], h["value"]))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -1183,3 +1246,39 @@ def explain_options_frame(reports: Sequence[ExplainReport], snapshots: Sequence[
                              **{k: f64 for k in EXPLAIN_COLUMNS}, "flags": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "start"], kind="stable").reset_index(drop=True)
+
+
+def var_level_columns(tail_probs) -> List[str]:
+    """The VaR and ES column names of var_frame for the tail probabilities `tail_probs`: var_0.05, es_0.05, ..."""
+    return [f"{k}_{float(tp):g}" for tp in tail_probs for k in ("var", "es")]
+
+
+def var_frame(reports: Sequence[VarReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per snapshot with quotes > 0, ordered by (underlying, date): columns underlying, date, spot, n_valid, var_<tp> and
+    es_<tp> per tail probability (losses are positive), worst_pnl and worst_start (the smallest scenario P&L and the first
+    snapshot of its pair; NaN / NaT without a valid scenario), value, gross, n_dead."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        worst = _host(p.worst)[keep].astype(np.int64)
+        has = worst >= 0
+        pnl = _host(p.pnl)[keep]
+        start = keep - p.lag - worst                                                        # H0
+        cols = {"underlying": p.underlying, "date": p.dates[keep], "spot": _host(r.spot)[keep],
+                "n_valid": _host(p.n_valid)[keep].astype(np.int32)}
+        var, es = _host(p.var)[keep], _host(p.es)[keep]
+        for n, tp in enumerate(p.tail_probs):
+            cols[f"var_{float(tp):g}"] = var[:, n]
+            cols[f"es_{float(tp):g}"] = es[:, n]
+        cols["worst_pnl"] = np.where(has, pnl[np.arange(len(keep)), np.maximum(worst, 0)], np.nan) if len(keep) else np.zeros(0)
+        cols["worst_start"] = pd.DatetimeIndex(p.dates[np.where(has, start, 0)]).where(has) if len(keep) else p.dates[:0]
+        value = _host(p.value)[keep]
+        cols["value"], cols["gross"] = value[:, 0], value[:, 1]
+        cols["n_dead"] = _host(p.n_dead)[keep].astype(np.int32)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64, ns = pd.Series(dtype=np.float64), pd.Series(dtype="datetime64[ns]")
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": ns, "spot": f64, "n_valid": pd.Series(dtype=np.int32),
+                             "worst_pnl": f64, "worst_start": ns, "value": f64, "gross": f64, "n_dead": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
