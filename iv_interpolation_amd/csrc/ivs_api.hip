@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/ivs.h"
 #include "ivs_arbitrage.hpp"
@@ -128,6 +129,29 @@ int check_query_launch(const char* fn, const char* noun, int64_t B, int32_t mT, 
     if (int rc = check_rows(fn, B, mT)) return rc;
     if (B > 0x7fffffffLL / Q) return fail(IVS_ERANGE, "%s: %lld x %lld %s exceed one launch", fn, (long long)B, (long long)Q, noun);
     return IVS_OK;
+}
+
+// ... and what their kernels' params take over from the args field for field: the names agree; svi_eval has no sides, and
+// neither it nor svi_greeks has quantities
+template <class P, class A>
+void set_query_fields(P& p, const A* a) {
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau;
+    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
+    p.mT = a->mT; p.strike_mode = a->strike_mode; p.Q = a->Q;
+    if constexpr (!std::is_same_v<P, ivs::EvalParams>) p.is_put = a->is_put;
+    if constexpr (!std::is_same_v<P, ivs::EvalParams> && !std::is_same_v<P, ivs::RiskParams>) p.qty = a->qty;
+}
+
+// items (scenario cells, scenarios) per workgroup of the kernels that split the n >= 1 items of each of B snapshots into runs:
+// all n, or the fewest runs of at most `cap`, while the snapshots alone give every CU `per_cu` workgroups, shorter runs below
+// that; `forced` > 0 is the tuning / testing override.  The sums of an item do not depend on the split.
+int items_per_wg(int64_t B, int n, int per_cu, int cap, int forced) {
+    int dev, cus;
+    current_device(dev, cus);
+    int64_t need = (per_cu * (int64_t)cus + B - 1) / B;
+    const int least = (n + cap - 1) / cap;
+    need = need < least ? least : (need > n ? n : need);
+    return forced > 0 ? forced : (int)((n + need - 1) / need);
 }
 
 }  // namespace
@@ -630,9 +654,7 @@ int ivs_svi_eval_f64(const ivs_eval_args* a, void*, size_t, void* stream) {
     if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->flags) return fail(IVS_EINVAL, "%s: null pointer", fn);
     if (int rc = check_query_launch(fn, "queries", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
     ivs::EvalParams p{};
-    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau;
-    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
-    p.mT = a->mT; p.strike_mode = a->strike_mode; p.Q = a->Q;
+    set_query_fields(p, a);
     p.nqb = (int32_t)((a->Q + ivs::SE_BLOCK - 1) / ivs::SE_BLOCK);
     p.w = a->w; p.vol = a->vol; p.call = a->call; p.put = a->put; p.fwd_var = a->fwd_var; p.g = a->g; p.local_vol = a->local_vol;
     p.flags = a->flags;
@@ -649,9 +671,7 @@ int ivs_svi_greeks_f64(const ivs_greeks_args* a, void*, size_t, void* stream) {
     if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->flags) return fail(IVS_EINVAL, "%s: null pointer", fn);
     if (int rc = check_query_launch(fn, "options", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
     ivs::RiskParams p{};
-    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put;
-    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
-    p.mT = a->mT; p.strike_mode = a->strike_mode; p.Q = a->Q;
+    set_query_fields(p, a);
     p.nqb = (int32_t)((a->Q + ivs::RK_BLOCK - 1) / ivs::RK_BLOCK);
     p.out[0] = a->price; p.out[1] = a->delta_ss; p.out[2] = a->delta_sm; p.out[3] = a->gamma_ss; p.out[4] = a->gamma_sm;
     p.out[5] = a->vega; p.out[6] = a->theta;
@@ -686,27 +706,15 @@ int ivs_svi_book_f64(const ivs_book_args* a, void*, size_t, void* stream) {
     if (ncell > 0 && a->B > 0x7fffffffLL / ncell)
         return fail(IVS_ERANGE, "%s: %lld x %d cells exceed one launch", fn, (long long)a->B, ncell);
     ivs::BookParams p{};
-    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put; p.qty = a->qty;
-    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
-    p.mT = a->mT; p.strike_mode = a->strike_mode; p.nA = a->nA; p.nV = a->nV; p.Q = a->Q;
+    set_query_fields(p, a);
+    p.nA = a->nA; p.nV = a->nV;
     for (int i = 0; ncell > 0 && i < a->nA; ++i) p.a[i] = a->spot_shocks[i];
     for (int k = 0; ncell > 0 && k < a->nV; ++k) p.v[k] = a->vol_shocks[k];
     p.net = a->net; p.n_dead = a->n_dead; p.pnl_ss = a->pnl_ss; p.pnl_sm = a->pnl_sm; p.cell_flags = a->cell_flags;
-    // cells per workgroup: a whole grid of up to 256 cells while the snapshots alone give every CU two workgroups, shorter runs
-    // below that.  The sums of a cell do not depend on the split.
-    int cpb = 0, nchunk = 1;
-    if (ncell > 0) {
-        int dev, cus;
-        current_device(dev, cus);
-        int64_t need = (2 * (int64_t)cus + a->B - 1) / a->B;
-        const int least = (ncell + ivs::RK_MAX_CELLS - 1) / ivs::RK_MAX_CELLS;
-        need = need < least ? least : (need > ncell ? ncell : need);
-        cpb = (int)((ncell + need - 1) / need);
-        if (a->cells_per_wg > 0) cpb = a->cells_per_wg;     // tuning / testing override
-        nchunk = (ncell + cpb - 1) / cpb;
-    }
-    p.cpb = cpb; p.nchunk = nchunk;
-    const int64_t grid = a->B * nchunk;                     // <= B * max(ncell, 1) < 2^31
+    // cells per workgroup: a whole grid of up to 256 cells while the snapshots alone give every CU two workgroups
+    p.cpb = ncell > 0 ? items_per_wg(a->B, ncell, 2, ivs::RK_MAX_CELLS, a->cells_per_wg) : 0;
+    p.nchunk = ncell > 0 ? (ncell + p.cpb - 1) / p.cpb : 1;
+    const int64_t grid = a->B * p.nchunk;                   // <= B * max(ncell, 1) < 2^31
     hipLaunchKernelGGL(ivs::svi_book_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
     return end_call("svi_book_kernel");
 }
@@ -721,9 +729,8 @@ int ivs_svi_explain_f64(const ivs_explain_args* a, void*, size_t, void* stream) 
         return fail(IVS_EINVAL, "%s: null pointer", fn);
     if (int rc = check_query_launch(fn, "options", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
     ivs::ExplainParams p{};
-    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put; p.qty = a->qty;
-    p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
-    p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.Q = a->Q;
+    set_query_fields(p, a);
+    p.lag = a->lag;
     p.out[0] = a->actual; p.out[1] = a->theta_pnl; p.out[2] = a->delta_ss; p.out[3] = a->gamma_ss; p.out[4] = a->vega_ss;
     p.out[5] = a->resid_ss; p.out[6] = a->delta_sm; p.out[7] = a->gamma_sm; p.out[8] = a->vega_sm; p.out[9] = a->resid_sm;
     p.net = a->net; p.n_dead = a->n_dead; p.flags = a->flags;
@@ -759,22 +766,15 @@ int ivs_svi_hsim_f64(const ivs_hsim_args* a, void*, size_t, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (a->stages != 2) {
         ivs::HsimParams p{};
-        p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau; p.is_put = a->is_put; p.qty = a->qty;
-        p.tq_stride = a->tq_stride; p.q_stride = a->q_stride; p.rate = a->rate;
-        p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.window = a->window; p.Q = a->Q;
+        set_query_fields(p, a);
+        p.lag = a->lag; p.window = a->window;
         p.pnl = a->pnl; p.scen_flags = a->scen_flags; p.value = a->value; p.n_dead = a->n_dead;
-        // scenarios per workgroup: the whole window while the snapshots alone give every CU sixteen workgroups, shorter runs
-        // below that, as ivs_svi_book_f64 spreads its cells.  Sixteen, not its two: a workgroup that takes 256 scenarios of a
-        // 1024-option book runs for milliseconds, and with only five rounds of them per CU the last round stands half empty
-        // (131.0 ms against 126.4 ms with runs of 128 or 64 on the bench of DESIGN.md section 19).  The sums of a scenario do
-        // not depend on the split.
-        int dev, cus;
-        current_device(dev, cus);
-        int64_t need = (16 * (int64_t)cus + a->B - 1) / a->B;
-        need = need < 1 ? 1 : (need > a->window ? a->window : need);
-        int spw = (int)((a->window + need - 1) / need);
-        if (a->scen_per_wg > 0) spw = a->scen_per_wg;           // tuning / testing override
-        p.spw = spw; p.nchunk = (a->window + spw - 1) / spw;
+        // scenarios per workgroup: the whole window while the snapshots alone give every CU sixteen workgroups.  Sixteen, not
+        // the book's two: a workgroup that takes 256 scenarios of a 1024-option book runs for milliseconds, and with only five
+        // rounds of them per CU the last round stands half empty (131.0 ms against 126.4 ms with runs of 128 or 64 on the
+        // bench of DESIGN.md section 19).
+        p.spw = items_per_wg(a->B, a->window, 16, a->window, a->scen_per_wg);
+        p.nchunk = (a->window + p.spw - 1) / p.spw;
         const int64_t grid = a->B * p.nchunk;                   // <= B * window < 2^31
         hipLaunchKernelGGL(ivs::svi_hsim_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, st, p);
         if (int rc = end_call("svi_hsim_kernel")) return rc;

@@ -10,7 +10,7 @@
 // inside each wavefront, the four wavefront sums through LDS as (s0 + s1) + (s2 + s3), the passes serially in the register of
 // the thread that owns the figure.  No atomics; a pair's bits depend on its two snapshots and on Q alone.
 //
-// Rule X8: contraction is off throughout, both prices come from rk_price on rk_surface's W and the three vols from xp_sigma, so
+// Rule X8: contraction is off throughout, both prices come from rk_price on rk_surface's W and the three vols from rk_sigma, so
 // a pair whose two ends carry the same bits yields the same sequence of IEEE operations on the same operands at both ends.
 #pragma once
 #include "ivs_risk.hpp"
@@ -32,12 +32,6 @@ struct ExplainParams {
     int32_t* flags;                                      // [P][Q]
 };
 
-// the vol of rule X1 at x with a placement's bracket and weight: sigma_1, sigma_0^ss and sigma_0^sm all come from here
-__device__ __forceinline__ double xp_sigma(const double* sl, const RkPoint& pt, double x, double tq) {
-#pragma clang fp contract(off)
-    return sqrt(rk_W(sl, pt, x) / tq);
-}
-
 __global__ __launch_bounds__(RK_BLOCK) void svi_explain_kernel(ExplainParams p) {
 #pragma clang fp contract(off)
     __shared__ double sl[2][ST_MAX_T * 6];
@@ -58,6 +52,7 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_explain_kernel(ExplainParams p) 
     bool degenerate = false;
     for (int64_t q0 = 0; q0 < p.Q; q0 += RK_BLOCK) {
         const int64_t q = q0 + tid;
+        // rk_option and RkOption::live spelled out: through them this kernel runs 0.5 % slower (profiles/book_refactor/bench.txt)
         const bool valid = q < p.Q;
         const double u = valid ? p.u[b0 * p.q_stride + q] : qnan();
         const double t0 = valid ? p.tau[b0 * p.q_stride + q] : qnan();
@@ -71,8 +66,7 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_explain_kernel(ExplainParams p) 
         const RkPoint c = rk_locate(sl[0], p.mT, S0, K, t1, p.rate, 1, unc, anyc);
         degenerate = un0 || !any0 || un1 || !any1;                       // the pair's: the same in every thread and pass
         const bool live = valid && a.ok && e.ok && c.ok && qty - qty == 0.0;                   // X2
-        const unsigned long long dm = __ballot(valid && !live);
-        if (lane == 0) dpart[wave] = __popcll(dm);
+        rk_dead_part(dpart, wave, lane, valid && !live);
 
         int32_t fl = a.fl | (e.fl << 8) | (c.fl << 16);                  // X5
         double o[XP_NET];
@@ -87,9 +81,9 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_explain_kernel(ExplainParams p) 
                 double We, We1, We2, Ve;
                 rk_surface(sl[1], e, We, We1, We2, Ve);
                 const double P1 = rk_price(S1, e.K * e.D, e.x, sqrt(We), put);
-                const double sg1 = xp_sigma(sl[1], e, e.x, t1);
-                const double sg_ss = xp_sigma(sl[0], c, c.x, t1);
-                const double sg_sm = xp_sigma(sl[0], c, e.x, t1);         // e.x = log(K / S1) - rate t1: the new moneyness
+                const double sg1 = rk_sigma(sl[1], e, e.x, t1);
+                const double sg_ss = rk_sigma(sl[0], c, c.x, t1);
+                const double sg_sm = rk_sigma(sl[0], c, e.x, t1);         // e.x = log(K / S1) - rate t1: the new moneyness
                 const double dt = t0 - t1;
                 // X3: a product that is a zero of either sign is written as +0.0
                 o[0] = P1 - g[0];
@@ -118,8 +112,8 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_explain_kernel(ExplainParams p) 
             if (lane == 0) npart[wave][k] = s;
         }
         __syncthreads();
-        if (tid < XP_NET) ntot = ntot + ((npart[0][tid] + npart[1][tid]) + (npart[2][tid] + npart[3][tid]));
-        dead += dpart[0] + dpart[1] + dpart[2] + dpart[3];
+        if (tid < XP_NET) ntot = ntot + rk_four([&](int w) { return npart[w][tid]; });
+        dead += rk_dead_sum(dpart);
         __syncthreads();
     }
     if (tid < XP_NET) p.net[b0 * XP_NET + tid] = degenerate ? qnan() : ntot;

@@ -1,6 +1,6 @@
 // Historical-simulation VaR and expected shortfall of a book per snapshot (rules H0-H9): every past pair
 // of snapshots (j, j + lag) is a scenario, applied to today's book with a full revaluation on the surface.  Everything is built
-// from the device functions of ivs_risk.hpp (rk_locate, rk_W, rk_surface, rk_price, rk_greeks, rk_wave_sum) and, underneath,
+// from the device functions of ivs_risk.hpp (rk_locate, rk_sigma, rk_surface, rk_price, rk_greeks, rk_wave_sum) and, underneath,
 // st_stage / st_bracket of ivs_svi_surface.hpp: this file adds the scenario's spot and vol (H1, H2) and the order statistics (H7).
 //
 // svi_hsim_kernel: a workgroup of four wavefronts owns one snapshot p and a run of scenarios.  Today's slices are staged in LDS
@@ -45,12 +45,6 @@ struct HsimTailParams {
     int32_t* n_valid; int32_t* worst;                    // [B]
 };
 
-// the vol of rule H2 at x with a snapshot's bracket and weight: sigma_now, sigma_a, sigma_b and the base's vol all come from here
-__device__ __forceinline__ double hs_sigma(const double* sl, const RkPoint& pt, double x, double tq) {
-#pragma clang fp contract(off)
-    return sqrt(rk_W(sl, pt, x) / tq);
-}
-
 __global__ __launch_bounds__(RK_BLOCK) void svi_hsim_kernel(HsimParams p) {
 #pragma clang fp contract(off)
     __shared__ double sl[ST_MAX_T * 6];                                  // today's slices
@@ -81,19 +75,15 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_hsim_kernel(HsimParams p) {
         int32_t tflag = 0, dead = 0;
         bool degenerate = false;
         for (int64_t q0 = 0; q0 < p.Q; q0 += RK_BLOCK) {
-            const int64_t q = q0 + tid;
-            const bool valid = q < p.Q;
-            const double u = valid ? p.u[b * p.q_stride + q] : qnan();
-            const double tq = valid ? p.tau[b * p.q_stride + q] : qnan();
-            const double qty = valid ? p.qty[q] : 0.0;
-            const bool put = valid && p.is_put ? p.is_put[q] != 0 : false;
+            const RkOption opt = rk_option(p, b, q0 + tid);
+            const double tq = opt.tau, qty = opt.qty;
+            const bool put = opt.put;
             bool unordered, any;
-            const RkPoint pt = rk_locate(sl, p.mT, S, u, tq, p.rate, p.strike_mode, unordered, any);
+            const RkPoint pt = rk_locate(sl, p.mT, S, opt.u, tq, p.rate, p.strike_mode, unordered, any);
             degenerate = unordered || !any;                              // the snapshot's: the same in every thread and pass
-            const bool live = valid && pt.ok && qty - qty == 0.0;        // G0
+            const bool live = opt.live(pt.ok);
             if (owner) {                                                 // H8
-                const unsigned long long dm = __ballot(valid && !live);
-                if (lane == 0) dpart[wave] = __popcll(dm);
+                rk_dead_part(dpart, wave, lane, opt.valid && !live);
                 double o[7];
                 o[0] = 0.0;
                 if (live && p.value) {
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_hsim_kernel(HsimParams p) {
             {
                 const double S1 = S * 1.0;
                 const double x1 = log(pt.K / S1) - pt.rt;
-                base = rk_price(S1, KD, x1, (hs_sigma(sl, pt, x1, tq) + 0.0) * sqt, put);
+                base = rk_price(S1, KD, x1, (rk_sigma(sl, pt, x1, tq) + 0.0) * sqt, put);
             }
             RkPoint ea;                                                  // the option on the start of the previous scenario
             bool una = false, anya = false;
@@ -137,7 +127,7 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_hsim_kernel(HsimParams p) {
                 if (!__builtin_amdgcn_readfirstlane((int)vd)) {
                     const double S1 = S * (Sb / Sa);                     // H1: the quotient first
                     const double x1 = log(pt.K / S1) - pt.rt;
-                    const double sg = hs_sigma(sl, pt, x1, tq) + (hs_sigma(hist[ib], eb, x1, tq) - hs_sigma(hist[ia], ea, x1, tq));       // H2
+                    const double sg = rk_sigma(sl, pt, x1, tq) + (rk_sigma(hist[ib], eb, x1, tq) - rk_sigma(hist[ia], ea, x1, tq));       // H2
                     const double pr = rk_price(S1, KD, x1, sg * sqt, put);
                     sum = rk_wave_sum(live ? qty * (pr - base) : 0.0);
                     f = __ballot(live && !(sg > 0.0)) != 0ull ? IVS_HS_NEG_VOL : 0;              // H5
@@ -145,13 +135,13 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_hsim_kernel(HsimParams p) {
                 if (lane == 0) { part[wave][c] = sum; pflag[wave][c] = f; }
             }
             __syncthreads();
-            if (tid < nce) {                                             // B5: (s0 + s1) + (s2 + s3), then the passes in turn
-                tot = tot + ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]));
-                tflag |= pflag[0][tid] | pflag[1][tid] | pflag[2][tid] | pflag[3][tid];
+            if (tid < nce) {                                             // B5: rk_four, then the passes in turn
+                tot = tot + rk_four([&](int w) { return part[w][tid]; });
+                tflag |= rk_four_or([&](int w) { return pflag[w][tid]; });
             }
             if (owner) {
-                if (tid < 2) vtot = vtot + ((vpart[0][tid] + vpart[1][tid]) + (vpart[2][tid] + vpart[3][tid]));
-                dead += dpart[0] + dpart[1] + dpart[2] + dpart[3];
+                if (tid < 2) vtot = vtot + rk_four([&](int w) { return vpart[w][tid]; });
+                dead += rk_dead_sum(dpart);
             }
             __syncthreads();
         }

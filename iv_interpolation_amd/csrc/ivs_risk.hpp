@@ -124,6 +124,12 @@ __device__ __forceinline__ double rk_W(const double* sl, const RkPoint& pt, doub
     return wl * pt.lam;
 }
 
+// the vol at x with a placement's bracket and weight: every vol of the book, explain (X1) and hsim (H2) kernels comes from here
+__device__ __forceinline__ double rk_sigma(const double* sl, const RkPoint& pt, double x, double tq) {
+#pragma clang fp contract(off)
+    return sqrt(rk_W(sl, pt, x) / tq);
+}
+
 // rule E3: W, W', W'' and V at the option's own x
 __device__ __forceinline__ void rk_surface(const double* sl, const RkPoint& pt, double& W, double& W1, double& W2, double& V) {
 #pragma clang fp contract(off)
@@ -225,6 +231,52 @@ __device__ __forceinline__ double rk_wave_sum(double v) {
     return v;
 }
 
+// rule B5, second level: what the four wavefronts left in LDS, s(w) = wavefront w's entry, as (s0 + s1) + (s2 + s3)
+template <class F>
+__device__ __forceinline__ double rk_four(F s) {
+#pragma clang fp contract(off)
+    return (s(0) + s(1)) + (s(2) + s(3));
+}
+template <class F>
+__device__ __forceinline__ int32_t rk_four_or(F s) {
+#pragma clang fp contract(off)
+    return s(0) | s(1) | s(2) | s(3);
+}
+
+// option q of a book as lane q % 256 of a pass sees it: NaN, a zero quantity and a call beyond Q
+struct RkOption {
+    double u, tau, qty;
+    bool valid, put;
+    // G0: a quantity that is not finite kills the option; ok = every placement of it is
+    __device__ __forceinline__ bool live(bool ok) const {
+#pragma clang fp contract(off)
+        return valid && ok && qty - qty == 0.0;
+    }
+};
+
+template <class P>
+__device__ __forceinline__ RkOption rk_option(const P& p, int64_t b, int64_t q) {
+#pragma clang fp contract(off)
+    RkOption o;
+    o.valid = q < p.Q;
+    o.u = o.valid ? p.u[b * p.q_stride + q] : qnan();
+    o.tau = o.valid ? p.tau[b * p.q_stride + q] : qnan();
+    o.qty = o.valid ? p.qty[q] : 0.0;
+    o.put = o.valid && p.is_put ? p.is_put[q] != 0 : false;
+    return o;
+}
+
+// the dead options of a pass: each wavefront counts its own into dpart, and after a barrier every thread has the pass's count
+__device__ __forceinline__ void rk_dead_part(int32_t* dpart, int wave, int lane, bool dead) {
+#pragma clang fp contract(off)
+    const unsigned long long dm = __ballot(dead);
+    if (lane == 0) dpart[wave] = __popcll(dm);
+}
+__device__ __forceinline__ int32_t rk_dead_sum(const int32_t* dpart) {
+#pragma clang fp contract(off)
+    return dpart[0] + dpart[1] + dpart[2] + dpart[3];
+}
+
 __global__ __launch_bounds__(RK_BLOCK) void svi_book_kernel(BookParams p) {
 #pragma clang fp contract(off)
     __shared__ double sl[ST_MAX_T * 6];
@@ -248,18 +300,14 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_book_kernel(BookParams p) {
     int32_t tflag = 0, dead = 0;
     bool degenerate = false;
     for (int64_t q0 = 0; q0 < p.Q; q0 += RK_BLOCK) {
-        const int64_t q = q0 + tid;
-        const bool valid = q < p.Q;
-        const double u = valid ? p.u[b * p.q_stride + q] : qnan();
-        const double tq = valid ? p.tau[b * p.q_stride + q] : qnan();
-        const double qty = valid ? p.qty[q] : 0.0;
-        const bool put = valid && p.is_put ? p.is_put[q] != 0 : false;
+        const RkOption opt = rk_option(p, b, q0 + tid);
+        const double tq = opt.tau, qty = opt.qty;
+        const bool put = opt.put;
         bool unordered, any;
-        const RkPoint pt = rk_locate(sl, p.mT, S, u, tq, p.rate, p.strike_mode, unordered, any);
+        const RkPoint pt = rk_locate(sl, p.mT, S, opt.u, tq, p.rate, p.strike_mode, unordered, any);
         degenerate = unordered || !any;                                  // the snapshot's: the same in every thread and pass
-        const bool live = valid && pt.ok && qty - qty == 0.0;            // G0: a quantity that is not finite kills the option
-        const unsigned long long dm = __ballot(valid && !live);
-        if (lane == 0) dpart[wave] = __popcll(dm);
+        const bool live = opt.live(pt.ok);
+        rk_dead_part(dpart, wave, lane, opt.valid && !live);
 
         if (first) {                                                     // B1
             double o[RK_NET];
@@ -280,13 +328,13 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_book_kernel(BookParams p) {
         // B2: the option's own state; the base goes through the code of a cell with both shocks zero (B4)
         const double KD = pt.K * pt.D;
         const double sqt = sqrt(tq);
-        const double sig0 = sqrt(rk_W(sl, pt, pt.x) / tq);
+        const double sig0 = rk_sigma(sl, pt, pt.x, tq);
         double base_ss = 0.0, base_sm = 0.0;
         {
             const double S1 = S * (1.0 + 0.0);
             const double x1 = log(pt.K / S1) - pt.rt;
             if (p.pnl_ss) base_ss = rk_price(S1, KD, x1, (sig0 + 0.0) * sqt, put);
-            if (p.pnl_sm) base_sm = rk_price(S1, KD, x1, (sqrt(rk_W(sl, pt, x1) / tq) + 0.0) * sqt, put);
+            if (p.pnl_sm) base_sm = rk_price(S1, KD, x1, (rk_sigma(sl, pt, x1, tq) + 0.0) * sqt, put);
         }
         int i = nc > 0 ? c0 / p.nV : 0;
         int k = nc > 0 ? c0 - i * p.nV : 0;
@@ -295,7 +343,7 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_book_kernel(BookParams p) {
             if (c == 0 || k == 0) {                                      // a new spot shock: the sticky-moneyness curve once
                 S1 = S * (1.0 + p.a[i]);
                 x1 = log(pt.K / S1) - pt.rt;
-                if (p.pnl_sm) sig1 = sqrt(rk_W(sl, pt, x1) / tq);
+                if (p.pnl_sm) sig1 = rk_sigma(sl, pt, x1, tq);
             }
             const double v = p.v[k];
             double s_ss = 0.0, s_sm = 0.0;
@@ -316,13 +364,13 @@ __global__ __launch_bounds__(RK_BLOCK) void svi_book_kernel(BookParams p) {
             if (++k == p.nV) { k = 0; ++i; }
         }
         __syncthreads();
-        if (tid < nc) {                                                  // B5: (s0 + s1) + (s2 + s3), then the passes in turn
-            tot_ss = tot_ss + ((part[0][tid][0] + part[1][tid][0]) + (part[2][tid][0] + part[3][tid][0]));
-            tot_sm = tot_sm + ((part[0][tid][1] + part[1][tid][1]) + (part[2][tid][1] + part[3][tid][1]));
-            tflag |= pflag[0][tid] | pflag[1][tid] | pflag[2][tid] | pflag[3][tid];
+        if (tid < nc) {                                                  // B5: rk_four, then the passes in turn
+            tot_ss = tot_ss + rk_four([&](int w) { return part[w][tid][0]; });
+            tot_sm = tot_sm + rk_four([&](int w) { return part[w][tid][1]; });
+            tflag |= rk_four_or([&](int w) { return pflag[w][tid]; });
         }
-        if (first && tid < RK_NET) ntot = ntot + ((npart[0][tid] + npart[1][tid]) + (npart[2][tid] + npart[3][tid]));
-        dead += dpart[0] + dpart[1] + dpart[2] + dpart[3];
+        if (first && tid < RK_NET) ntot = ntot + rk_four([&](int w) { return npart[w][tid]; });
+        dead += rk_dead_sum(dpart);
         __syncthreads();
     }
 

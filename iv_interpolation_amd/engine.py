@@ -550,21 +550,10 @@ def svi_eval(params, Tq, spot, rate, u, tau, *, strike_mode: int = 0, want=EVAL_
     want: which of EVAL_OUTPUTS to compute; one left out is neither computed nor written (None in the result).
     `out`: optional dict of preallocated outputs (float64 [B,Q] per value, flags int32 [B,Q]).
     Returns dict(w, vol, call, put, fwd_var, g, local_vol, flags) of device tensors; the flags are the _lib.SE_* bits."""
-    if strike_mode not in (0, 1):
-        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    _check_strike_mode(strike_mode)
     want = _wanted(want, EVAL_OUTPUTS)
-    torch = require_device()
-    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
-    u, tau, _, _, Q = _option_queries(torch, B, u, tau, None)
-    shapes = {k: ((B, Q), torch.float64, k in want) for k in EVAL_OUTPUTS}
-    shapes["flags"] = ((B, Q), torch.int32, True)
-    out = _outputs(torch, out, shapes, params.device)
-    a = _slice_fields(_lib.EvalArgs(), params, Tq, spot, rate)
-    _query_fields(a, u, tau, strike_mode)
-    for k in shapes:
-        setattr(a, k, _ptr(out[k]))
-    _call(torch, "ivs_svi_eval_f64", a, stream, params, Tq, spot, u, tau, *out.values())
-    return {k: out[k] for k in shapes}
+    return _option_call("ivs_svi_eval_f64", _lib.EvalArgs(), params, Tq, spot, rate, u, tau, strike_mode, out, stream,
+                        lambda torch, B, Q: _per_option(torch, (B, Q), EVAL_OUTPUTS, want))[1]
 
 
 GREEK_OUTPUTS = ("price", "delta_ss", "delta_sm", "gamma_ss", "gamma_sm", "vega", "theta")
@@ -594,6 +583,45 @@ def _option_queries(torch, B, u, tau, is_put, qty=None):
     return u, tau, is_put, qty, Q
 
 
+def _check_strike_mode(strike_mode):
+    if strike_mode not in (0, 1):
+        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+
+
+def _per_option(torch, shape, names, want):
+    """The shapes (as _outputs takes them) of one float64 value per option and name, those in `want` alone, and the flags."""
+    return {**{k: (shape, torch.float64, k in want) for k in names}, "flags": (shape, torch.int32, True)}
+
+
+def _option_call(name, a, params, Tq, spot, rate, u, tau, strike_mode, out, stream, shapes, is_put=None, qty=None, **fields):
+    """The chain svi_eval, svi_greeks, svi_book, svi_explain and svi_hsim share: the input checks, the outputs (shapes(torch, B,
+    Q) describes them as _outputs takes them), the args struct `a` filled with the slices, the options, the call's own
+    `fields` and the outputs' pointers, and the C call `name`.  Returns torch, the result dict and B, mT, Q."""
+    torch = require_device()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
+    shapes = shapes(torch, B, Q)
+    out = _outputs(torch, out, shapes, params.device)
+    _slice_fields(a, params, Tq, spot, rate)
+    _query_fields(a, u, tau, strike_mode)
+    for k, v in fields.items():
+        setattr(a, k, v)
+    for k, t in (("is_put", is_put), ("qty", qty), *((k, out[k]) for k in shapes)):
+        if t is not None:
+            setattr(a, k, _ptr(t))
+    _call(torch, name, a, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
+    return torch, {k: out[k] for k in shapes}, B, mT, Q
+
+
+def _fill(torch, stream, out, values):
+    """The C call was a no-op (no slice or no option): the wrapper defines the result and writes it on the caller's stream.
+    values: {key: number or tensor}, or a function that forms that dict on the stream; an output not wanted is passed over."""
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        for k, v in (values() if callable(values) else values).items():
+            if out[k] is not None:
+                out[k].copy_(v) if torch.is_tensor(v) else out[k].fill_(v)
+
+
 def svi_greeks(params, Tq, spot, rate, u, tau, *, is_put=None, strike_mode: int = 0, want=GREEK_OUTPUTS, out=None, stream=None):
     """Smile-aware Greeks of options on the surface of the raw SVI slices (ivs_svi_greeks_f64; rules G0-G6 of DESIGN.md section
     17).  params, Tq, spot, rate, u, tau, strike_mode as in svi_eval; is_put uint8 / bool [Q] (one side per option, shared by
@@ -603,27 +631,14 @@ def svi_greeks(params, Tq, spot, rate, u, tau, *, is_put=None, strike_mode: int 
     With mT == 0 the C call writes nothing and the wrapper fills NaN and DEAD itself.
     Returns dict(price, delta_ss, delta_sm, gamma_ss, gamma_sm, vega, theta, flags) of device tensors; the flags are the
     _lib.SE_* bits SHORT, LONG, NEG_FWD, DEAD, UNORDERED."""
-    if strike_mode not in (0, 1):
-        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    _check_strike_mode(strike_mode)
     want = _wanted(want, GREEK_OUTPUTS)
-    torch = require_device()
-    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
-    u, tau, is_put, _, Q = _option_queries(torch, B, u, tau, is_put)
-    shapes = {k: ((B, Q), torch.float64, k in want) for k in GREEK_OUTPUTS}
-    shapes["flags"] = ((B, Q), torch.int32, True)
-    out = _outputs(torch, out, shapes, params.device)
-    a = _slice_fields(_lib.GreeksArgs(), params, Tq, spot, rate)
-    _query_fields(a, u, tau, strike_mode)
-    a.is_put = _ptr(is_put)
-    for k in shapes:
-        setattr(a, k, _ptr(out[k]))
-    _call(torch, "ivs_svi_greeks_f64", a, stream, params, Tq, spot, u, tau, is_put, *out.values())
-    if mT == 0:                                              # the C call is a no-op; without a slice every option is dead (E1)
-        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-            for k in want:
-                out[k].fill_(float("nan"))
-            out["flags"].fill_(_lib.SE_DEAD)
-    return {k: out[k] for k in shapes}
+    torch, out, _, mT, _ = _option_call(
+        "ivs_svi_greeks_f64", _lib.GreeksArgs(), params, Tq, spot, rate, u, tau, strike_mode, out, stream,
+        lambda torch, B, Q: _per_option(torch, (B, Q), GREEK_OUTPUTS, want), is_put)
+    if mT == 0:                                              # without a slice every option is dead (E1)
+        _fill(torch, stream, out, {**dict.fromkeys(GREEK_OUTPUTS, float("nan")), "flags": _lib.SE_DEAD})
+    return out
 
 
 def book_shocks(spot_shocks, vol_shocks):
@@ -654,36 +669,22 @@ def svi_book(params, Tq, spot, rate, u, tau, qty, spot_shocks=DEFAULT_SPOT_SHOCK
     degenerate (NaN, n_dead = Q, cell flags 0), and a book without options has 0 in every sum, count and flag.
     Returns dict(net, n_dead, pnl_ss, pnl_sm, cell_flags) of device tensors; net's columns are NET_COLUMNS, the cell flags the
     _lib.SB_* bits."""
-    if strike_mode not in (0, 1):
-        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    _check_strike_mode(strike_mode)
     want = _wanted(want, BOOK_OUTPUTS)
     sa, sv = book_shocks(spot_shocks, vol_shocks)
-    torch = require_device()
-    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
-    u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
     nA, nV = len(sa), len(sv)
-    shapes = {"net": ((B, 8), torch.float64, True), "n_dead": ((B,), torch.int32, True),
-              "pnl_ss": ((B, nA, nV), torch.float64, "pnl_ss" in want), "pnl_sm": ((B, nA, nV), torch.float64, "pnl_sm" in want),
-              "cell_flags": ((B, nA, nV), torch.int32, True)}
-    out = _outputs(torch, out, shapes, params.device)
-    a = _slice_fields(_lib.BookArgs(), params, Tq, spot, rate)
-    _query_fields(a, u, tau, strike_mode)
-    a.is_put, a.qty = _ptr(is_put), _ptr(qty)
-    a.spot_shocks, a.nA = _doubles(sa), nA
-    a.vol_shocks, a.nV = _doubles(sv), nV
-    for k in shapes:
-        setattr(a, k, _ptr(out[k]))
-    a.cells_per_wg = int(cells_per_wg)
-    _call(torch, "ivs_svi_book_f64", a, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
-    if B > 0 and (mT == 0 or Q == 0):                        # the C call is a no-op: the result is defined here
+
+    def shapes(torch, B, Q):
+        return {"net": ((B, 8), torch.float64, True), "n_dead": ((B,), torch.int32, True),
+                "pnl_ss": ((B, nA, nV), torch.float64, "pnl_ss" in want), "pnl_sm": ((B, nA, nV), torch.float64, "pnl_sm" in want),
+                "cell_flags": ((B, nA, nV), torch.int32, True)}
+    torch, out, B, mT, Q = _option_call(
+        "ivs_svi_book_f64", _lib.BookArgs(), params, Tq, spot, rate, u, tau, strike_mode, out, stream, shapes, is_put, qty,
+        spot_shocks=_doubles(sa), nA=nA, vol_shocks=_doubles(sv), nV=nV, cells_per_wg=int(cells_per_wg))
+    if B > 0 and (mT == 0 or Q == 0):
         empty = float("nan") if mT == 0 else 0.0             # B1: no live slice -> NaN and n_dead = Q; a book without options is worth 0
-        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-            out["net"].fill_(empty)
-            out["n_dead"].fill_(Q if mT == 0 else 0)
-            out["cell_flags"].zero_()
-            for k in want:
-                out[k].fill_(empty)
-    return {k: out[k] for k in shapes}
+        _fill(torch, stream, out, {"net": empty, "n_dead": Q if mT == 0 else 0, "cell_flags": 0, "pnl_ss": empty, "pnl_sm": empty})
+    return out
 
 
 EXPLAIN_OUTPUTS = ("actual", "theta_pnl", "delta_ss", "gamma_ss", "vega_ss", "resid_ss", "delta_sm", "gamma_sm", "vega_sm", "resid_sm")
@@ -705,34 +706,23 @@ def svi_explain(params, Tq, spot, rate, u, tau, qty, *, lag: int = 1, is_put=Non
     count.
     Returns dict(the ten values, flags, net, n_dead) of device tensors; net's columns are EXPLAIN_NET_COLUMNS, the flags the
     _lib.SE_* bits of the three placements in bits 0-7, 8-15 and 16-23."""
-    if strike_mode not in (0, 1):
-        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    _check_strike_mode(strike_mode)
     if int(lag) != lag or lag < 1:
         raise ValueError(f"lag {lag!r} is not an integer >= 1")
     want = _wanted(want, EXPLAIN_OUTPUTS)
-    torch = require_device()
-    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
-    u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
-    P = max(B - int(lag), 0)
-    shapes = {k: ((P, Q), torch.float64, k in want) for k in EXPLAIN_OUTPUTS}
-    shapes.update(flags=((P, Q), torch.int32, True), net=((P, 12), torch.float64, True), n_dead=((P,), torch.int32, True))
-    out = _outputs(torch, out, shapes, params.device)
-    a = _slice_fields(_lib.ExplainArgs(), params, Tq, spot, rate)
-    _query_fields(a, u, tau, strike_mode)
-    a.is_put, a.qty, a.lag = _ptr(is_put), _ptr(qty), int(lag)
-    for k in shapes:
-        setattr(a, k, _ptr(out[k]))
-    _call(torch, "ivs_svi_explain_f64", a, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
-    if P > 0 and (mT == 0 or Q == 0):                        # the C call is a no-op: the result is defined here
+
+    def shapes(torch, B, Q):
+        P = max(B - int(lag), 0)
+        return {**_per_option(torch, (P, Q), EXPLAIN_OUTPUTS, want),
+                "net": ((P, 12), torch.float64, True), "n_dead": ((P,), torch.int32, True)}
+    torch, out, B, mT, Q = _option_call(
+        "ivs_svi_explain_f64", _lib.ExplainArgs(), params, Tq, spot, rate, u, tau, strike_mode, out, stream, shapes, is_put, qty,
+        lag=int(lag))
+    if B > lag and (mT == 0 or Q == 0):
         empty = float("nan") if mT == 0 else 0.0             # X2: no live slice -> NaN and n_dead = Q; a book without options is worth 0
-        dead = _lib.SE_DEAD | _lib.SE_DEAD << 8 | _lib.SE_DEAD << 16
-        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-            out["net"].fill_(empty)
-            out["n_dead"].fill_(Q if mT == 0 else 0)
-            out["flags"].fill_(dead)
-            for k in want:
-                out[k].fill_(float("nan"))
-    return {k: out[k] for k in shapes}
+        _fill(torch, stream, out, {**dict.fromkeys(EXPLAIN_OUTPUTS, float("nan")), "net": empty, "n_dead": Q if mT == 0 else 0,
+                                   "flags": _lib.SE_DEAD | _lib.SE_DEAD << 8 | _lib.SE_DEAD << 16})
+    return out
 
 
 DEFAULT_TAIL_PROBS = (0.05, 0.01)
@@ -774,44 +764,34 @@ def svi_hsim(params, Tq, spot, rate, u, tau, qty, *, lag: int = 1, window: int =
     slice every snapshot is degenerate (every existing scenario VOID_PAIR and NaN, n_valid 0, n_dead = Q, NaN in var / es /
     value), and a book without options has +0.0 in every existing scenario, VaR, ES and value.
     Returns dict(pnl, scen_flags, var, es, n_valid, n_dead, worst, value) of device tensors; the flags are the _lib.HS_* bits."""
-    if strike_mode not in (0, 1):
-        raise ValueError(f"strike_mode {strike_mode!r} is neither 0 (moneyness) nor 1 (strike)")
+    _check_strike_mode(strike_mode)
     if stages not in (0, 1, 2):
         raise ValueError(f"stages {stages!r} is not 0, 1 or 2")
     lag, window, tp, min_scen, scen_per_wg = hsim_settings(lag, window, tail_probs, min_scen, scen_per_wg)
-    torch = require_device()
-    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
-    u, tau, is_put, qty, Q = _option_queries(torch, B, u, tau, is_put, qty)
     nL = len(tp)
-    i32, f64 = torch.int32, torch.float64
-    shapes = {"pnl": ((B, window), f64, True), "scen_flags": ((B, window), i32, True), "var": ((B, nL), f64, True),
-              "es": ((B, nL), f64, True), "n_valid": ((B,), i32, True), "n_dead": ((B,), i32, True), "worst": ((B,), i32, True),
-              "value": ((B, 2), f64, bool(value))}
-    out = _outputs(torch, out, shapes, params.device)
-    a = _slice_fields(_lib.HsimArgs(), params, Tq, spot, rate)
-    _query_fields(a, u, tau, strike_mode)
-    a.is_put, a.qty, a.lag, a.window = _ptr(is_put), _ptr(qty), lag, window
-    a.tail_probs, a.nL, a.min_scen, a.scen_per_wg, a.stages = _doubles(tp), nL, min_scen, scen_per_wg, int(stages)
-    for k in shapes:
-        setattr(a, k, _ptr(out[k]))
-    _call(torch, "ivs_svi_hsim_f64", a, stream, params, Tq, spot, u, tau, is_put, qty, *out.values())
-    if B > 0 and (mT == 0 or Q == 0):                        # the C call is a no-op: the result is defined here (H9)
-        nan = float("nan")
-        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-            n_p = (torch.arange(B, device=params.device) - lag + 1).clamp(0, window)
-            exists = torch.arange(window, device=params.device)[None, :] < n_p[:, None]
-            here = torch.full((), _lib.HS_VOID_PAIR if mT == 0 else 0, dtype=i32, device=params.device)
-            out["scen_flags"].copy_(torch.where(exists, here, torch.full_like(here, _lib.HS_ABSENT)))
-            out["pnl"].copy_(torch.where(exists & (mT > 0), 0.0, nan))
-            ranked = (n_p >= min_scen) & (mT > 0)
-            for k in ("var", "es"):
-                out[k].copy_(torch.where(ranked[:, None], 0.0, nan).expand(B, nL))
-            out["n_valid"].copy_(n_p if mT > 0 else torch.zeros_like(n_p))
-            out["worst"].copy_(torch.where((n_p > 0) & (mT > 0), 0, -1))
-            out["n_dead"].fill_(Q if mT == 0 else 0)
-            if out["value"] is not None:
-                out["value"].fill_(nan if mT == 0 else 0.0)
-    return {k: out[k] for k in shapes}
+
+    def shapes(torch, B, Q):
+        i32, f64 = torch.int32, torch.float64
+        return {"pnl": ((B, window), f64, True), "scen_flags": ((B, window), i32, True), "var": ((B, nL), f64, True),
+                "es": ((B, nL), f64, True), "n_valid": ((B,), i32, True), "n_dead": ((B,), i32, True), "worst": ((B,), i32, True),
+                "value": ((B, 2), f64, bool(value))}
+    torch, out, B, mT, Q = _option_call(
+        "ivs_svi_hsim_f64", _lib.HsimArgs(), params, Tq, spot, rate, u, tau, strike_mode, out, stream, shapes, is_put, qty,
+        lag=lag, window=window, tail_probs=_doubles(tp), nL=nL, min_scen=min_scen, scen_per_wg=scen_per_wg, stages=int(stages))
+
+    def empty():                                             # H9
+        nan, device = float("nan"), out["pnl"].device
+        n_p = (torch.arange(B, device=device) - lag + 1).clamp(0, window)
+        exists = torch.arange(window, device=device)[None, :] < n_p[:, None]
+        here = torch.full((), _lib.HS_VOID_PAIR if mT == 0 else 0, dtype=torch.int32, device=device)
+        tail = torch.where(((n_p >= min_scen) & (mT > 0))[:, None], 0.0, nan).expand(B, nL)
+        return {"scen_flags": torch.where(exists, here, torch.full_like(here, _lib.HS_ABSENT)),
+                "pnl": torch.where(exists & (mT > 0), 0.0, nan), "var": tail, "es": tail,
+                "n_valid": n_p if mT > 0 else torch.zeros_like(n_p), "worst": torch.where((n_p > 0) & (mT > 0), 0, -1),
+                "n_dead": Q if mT == 0 else 0, "value": nan if mT == 0 else 0.0}
+    if B > 0 and (mT == 0 or Q == 0):
+        _fill(torch, stream, out, empty)
+    return out
 
 
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):

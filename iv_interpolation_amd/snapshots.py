@@ -41,6 +41,7 @@ import pandas as pd
 from . import engine, synth
 from .engine import DEFAULT_DELTAS, delta_targets      # rule D3: 10d put, 25d put, ATM, 25d call, 10d call
 from .engine import DEFAULT_LEVELS, DEFAULT_PROBS, distribution_targets   # rule P9 and the host-side checks of section 13
+from .engine import EXPLAIN_NET_COLUMNS, EXPLAIN_OUTPUTS as EXPLAIN_COLUMNS, GREEK_OUTPUTS as GREEK_COLUMNS   # the figures' names
 
 YEAR_NS = 365 * 86400 * 10**9       # S2: E_c = date + time_to_maturity x YEAR, YEAR = 365 days (the synthetic data's convention)
 MINUTE_NS = 60 * 10**9
@@ -232,10 +233,6 @@ class RiskReport:
     pnl_ss: object                   # [B, nA, nV] sticky strike
     pnl_sm: object                   # [B, nA, nV] sticky moneyness
     cell_flags: object               # [B, nA, nV] int32, IVS_SB_*
-
-
-EXPLAIN_COLUMNS = ("actual", "theta_pnl", "delta_ss", "gamma_ss", "vega_ss", "resid_ss", "delta_sm", "gamma_sm", "vega_sm", "resid_sm")
-EXPLAIN_NET_COLUMNS = EXPLAIN_COLUMNS + ("value", "gross")
 
 
 @dataclass
@@ -604,6 +601,28 @@ class SnapshotSurfaceBuilder:
         tau[:, np.asarray(e.isna())] = np.nan
         return tau
 
+    def _book(self, book: pd.DataFrame, slices, sided: bool = True, settings=None):
+        """The book frame of price() (sided=False: strike and expiry) or of risk(), explain() and var() (callput and quantity
+        too), checked and parsed, and the slices to place it on (slices: the arguments of _slices).  The steps come in this
+        order: a missing column (KeyError), the stage's own settings (settings() raises ValueError), callput, the slices, the
+        numbers and dates.  Returns the SVI reports, strikes, expiry, is_put, qty (None, None when not sided) and what
+        settings() returned."""
+        for c in ("strike", "expiry") + (("callput", "quantity") if sided else ()):
+            if c not in book.columns:
+                raise KeyError(c)
+        own = settings() if settings else None
+        is_put = qty = None
+        if sided:
+            side = book["callput"].astype(str).str.lower().str[:1]
+            if not side.isin(["c", "p"]).all():
+                raise ValueError("callput must start with c or p")
+            is_put = (side == "p").to_numpy(bool)
+        svi_reports = self._slices(*slices)
+        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
+        if sided:
+            qty = pd.to_numeric(book["quantity"], errors="coerce").to_numpy(np.float64)
+        return svi_reports, strikes, pd.DatetimeIndex(pd.to_datetime(book["expiry"])), is_put, qty, own
+
     def calendar(self, results: Sequence[SnapshotSurfaces], svi_reports=None, rate: float = 0.0, rounds: int = 0) -> List[CalendarReport]:
         """Calendar report between the SVI slices of every surface of `results` (rules T1-T4, C1-C6): one CalendarReport per
         underlying, arrays on the device.  svi_reports: the SviReports of svi(results, rate) to read the slices from; None
@@ -624,12 +643,7 @@ class SnapshotSurfaceBuilder:
         frame with the columns strike and expiry (timestamps; naive ones are read in the time zone of the snapshots); the
         time to expiry is (expiry - snapshot date) / YEAR per snapshot, and an expired option is DEAD.  svi_reports as for
         calendar()."""
-        for c in ("strike", "expiry"):
-            if c not in book.columns:
-                raise KeyError(c)
-        svi_reports = self._slices(results, svi_reports, rate, rounds)
-        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
-        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
+        svi_reports, strikes, expiry, _, _, _ = self._book(book, (results, svi_reports, rate, rounds), sided=False)
         be = self._backend or HipBackend()
         reports = []
         for r, v in zip(results, svi_reports):
@@ -650,19 +664,9 @@ class SnapshotSurfaceBuilder:
         -20 % ... +20 % in steps of 5 %; vol_shocks: absolute moves of the vol, None = -0.10, -0.05, 0, +0.05, +0.10.
         svi_reports as for calendar()."""
         from .engine import DEFAULT_SPOT_SHOCKS, DEFAULT_VOL_SHOCKS, book_shocks
-        for c in ("strike", "expiry", "callput", "quantity"):
-            if c not in book.columns:
-                raise KeyError(c)
-        sa, sv = book_shocks(DEFAULT_SPOT_SHOCKS if spot_shocks is None else spot_shocks,
-                             DEFAULT_VOL_SHOCKS if vol_shocks is None else vol_shocks)
-        side = book["callput"].astype(str).str.lower().str[:1]
-        if not side.isin(["c", "p"]).all():
-            raise ValueError("callput must start with c or p")
-        is_put = (side == "p").to_numpy(bool)
-        svi_reports = self._slices(results, svi_reports, rate, rounds)
-        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
-        qty = pd.to_numeric(book["quantity"], errors="coerce").to_numpy(np.float64)
-        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
+        svi_reports, strikes, expiry, is_put, qty, (sa, sv) = self._book(
+            book, (results, svi_reports, rate, rounds), settings=lambda: book_shocks(
+                DEFAULT_SPOT_SHOCKS if spot_shocks is None else spot_shocks, DEFAULT_VOL_SHOCKS if vol_shocks is None else vol_shocks))
         be = self._backend or HipBackend()
         reports = []
         for r, v in zip(results, svi_reports):
@@ -681,20 +685,11 @@ class SnapshotSurfaceBuilder:
         X0-X9): one ExplainReport per underlying with the realised change of every option's price split into theta, delta,
         gamma, vega and a remainder under sticky strike and under sticky moneyness, and the book's sums.  book: risk()'s
         frame.  lag: an integer >= 1; an underlying with lag or fewer snapshots has no pair.  svi_reports as for calendar()."""
-        for c in ("strike", "expiry", "callput", "quantity"):
-            if c not in book.columns:
-                raise KeyError(c)
-        if int(lag) != lag or lag < 1:
-            raise ValueError(f"lag {lag!r} is not an integer >= 1")
+        def whole_lag():
+            if int(lag) != lag or lag < 1:
+                raise ValueError(f"lag {lag!r} is not an integer >= 1")
+        svi_reports, strikes, expiry, is_put, qty, _ = self._book(book, (results, svi_reports, rate, rounds), settings=whole_lag)
         lag = int(lag)
-        side = book["callput"].astype(str).str.lower().str[:1]
-        if not side.isin(["c", "p"]).all():
-            raise ValueError("callput must start with c or p")
-        is_put = (side == "p").to_numpy(bool)
-        svi_reports = self._slices(results, svi_reports, rate, rounds)
-        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
-        qty = pd.to_numeric(book["quantity"], errors="coerce").to_numpy(np.float64)
-        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
         be = self._backend or HipBackend()
         reports = []
         for r, v in zip(results, svi_reports):
@@ -715,18 +710,8 @@ class SnapshotSurfaceBuilder:
         probabilities (0.05 = the 95 % VaR); a snapshot with fewer than min_scenarios valid scenarios has NaN.  book: risk()'s
         frame.  svi_reports as for calendar()."""
         from .engine import hsim_settings
-        for c in ("strike", "expiry", "callput", "quantity"):
-            if c not in book.columns:
-                raise KeyError(c)
-        lag, window, tp, min_scenarios, _ = hsim_settings(lag, window, tail_probs, min_scenarios)
-        side = book["callput"].astype(str).str.lower().str[:1]
-        if not side.isin(["c", "p"]).all():
-            raise ValueError("callput must start with c or p")
-        is_put = (side == "p").to_numpy(bool)
-        svi_reports = self._slices(results, svi_reports, rate, rounds)
-        strikes = pd.to_numeric(book["strike"], errors="coerce").to_numpy(np.float64)
-        qty = pd.to_numeric(book["quantity"], errors="coerce").to_numpy(np.float64)
-        expiry = pd.DatetimeIndex(pd.to_datetime(book["expiry"]))
+        svi_reports, strikes, expiry, is_put, qty, (lag, window, tp, min_scenarios, _) = self._book(
+            book, (results, svi_reports, rate, rounds), settings=lambda: hsim_settings(lag, window, tail_probs, min_scenarios))
         be = self._backend or HipBackend()
         reports = []
         for r, v in zip(results, svi_reports):
@@ -1116,9 +1101,6 @@ def listed_book(data, quantity: float = 1.0) -> pd.DataFrame:
     return pd.DataFrame({"symbol": sym.to_numpy(), "underlying": sym.str.lower().str.split("-").str[0].to_numpy(),
                          "strike": strike.to_numpy(np.float64), "expiry": expiry, "callput": side.to_numpy(),
                          "quantity": float(quantity)}).reset_index(drop=True)
-
-
-GREEK_COLUMNS = ("price", "delta_ss", "delta_sm", "gamma_ss", "gamma_sm", "vega", "theta")
 
 
 def risk_frame(reports: Sequence[RiskReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:

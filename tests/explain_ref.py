@@ -27,14 +27,6 @@ def pair_inputs(params, Tq, spot, u, tau, lag):
                 u0=pick(u, i0), tau0=pick(tau, i0), tau1=pick(tau, i1))
 
 
-def _sigma(L, x, xs):
-    """sqrt(W / tau) at x with the placement's bracket and weight, and its scale: the one function of rule X8."""
-    s = R.surface(L, x, xs)
-    with np.errstate(all="ignore"):
-        sig = np.sqrt(s["w"] / L["tq"])
-        return sig, sig * (s["sw"] / (2.0 * s["w"]) + 2.0)
-
-
 def restate_explain(params, Tq, spot, rate, u, tau, qty, lag=1, is_put=None, strike_mode=0, margins=False):
     """Rules X0-X9.  Returns the ten values [P,Q], flags [P,Q], net [P,12], n_dead [P], scale_<key> of every value and
     scale_net (in eps), and for the tests: live, degenerate, a / b (the restated Greeks of the two ends), K, dS, dt, sig1,
@@ -58,9 +50,9 @@ def restate_explain(params, Tq, spot, rate, u, tau, qty, lag=1, is_put=None, str
         b = R.restate_greeks(E["params1"], E["Tq1"], S1, rate, K, t1, is_put, 1)                              # X1 (b)
         La, Lb = a["loc"], b["loc"]
         Lc = R.locate(E["params0"], E["Tq0"], S0, rate, K, t1, 1)                                             # X1 (c)
-        sig1, dsig1 = _sigma(Lb, Lb["x"], Lb["xs"])
-        sig_ss, dsig_ss = _sigma(Lc, Lc["x"], Lc["xs"])
-        sig_sm, dsig_sm = _sigma(Lc, Lb["x"], Lb["xs"])
+        sig1, dsig1 = R.sigma(Lb, Lb["x"], Lb["xs"])
+        sig_ss, dsig_ss = R.sigma(Lc, Lc["x"], Lc["xs"])
+        sig_sm, dsig_sm = R.sigma(Lc, Lb["x"], Lb["xs"])
         live = a["ok"] & b["ok"] & Lc["ok"] & np.isfinite(qty)[None, :]       # X2
         deg = (La["degenerate"] | Lb["degenerate"]) & (Q > 0)
         flags = (a["flags"] | (Lb["flags"] << 8) | (Lc["flags"] << 16)).astype(np.int32)        # X5

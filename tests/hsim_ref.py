@@ -51,14 +51,6 @@ def _rows(L, idx):
     return {k: (v[idx] if isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == B else v) for k, v in L.items()} | {"B": len(idx)}
 
 
-def _sigma(L, x, xs):
-    """sqrt(W / tau) at x with a snapshot's bracket and weight, and its scale: the one function of rule H2."""
-    s = R.surface(L, x, xs)
-    with np.errstate(all="ignore"):
-        sig = np.sqrt(s["w"] / L["tq"])
-        return sig, sig * (s["sw"] / (2.0 * s["w"]) + 2.0)
-
-
 def restate_hsim(params, Tq, spot, rate, u, tau, qty, lag=1, window=256, tail_probs=(0.05, 0.01), min_scen=20, is_put=None,
                  strike_mode=0, margins=False, keep=False):
     """Rules H0-H9.  Returns pnl, scen_flags [B,window], var, es [B,nL], n_valid, n_dead, worst [B], value [B,2], the units
@@ -112,10 +104,10 @@ def restate_hsim(params, Tq, spot, rate, u, tau, qty, lag=1, window=256, tail_pr
                 lk = np.log(K / S1)
                 x1 = lk - rt
                 xs1 = 3.0 + fS + np.abs(lk) + 2.0 * np.abs(rt)
-                sg, dsg = _sigma(Lp, x1, xs1)
+                sg, dsg = R.sigma(Lp, x1, xs1)
                 if ends:
-                    sb, dsb = _sigma(Lb, x1, xs1)
-                    sa, dsa = _sigma(La, x1, xs1)
+                    sb, dsb = R.sigma(Lb, x1, xs1)
+                    sa, dsa = R.sigma(La, x1, xs1)
                     d = sb - sa
                     sg = sg + d
                     dsg = dsg + dsb + dsa + np.abs(d) + np.abs(sg)

@@ -102,6 +102,14 @@ def surface(L, x, xs, derivs=False):
     return out
 
 
+def sigma(L, x, xs):
+    """sqrt(W / tau) at x with a placement's bracket and weight, and its scale: the one function of rules X8 and H2."""
+    s = surface(L, x, xs)
+    with np.errstate(all="ignore"):
+        sig = np.sqrt(s["w"] / L["tq"])
+        return sig, sig * (s["sw"] / (2.0 * s["w"]) + 2.0)
+
+
 def price(S, fS, KD, fKD, x, xs, th, dth, put):
     """Rule G1 at (S, x, theta) and its scale; fS, fKD: the relative errors of S and K D, dth: the error of theta, in eps."""
     with np.errstate(all="ignore"):
