@@ -38,6 +38,7 @@ IMPLIED_TABLE = "iv_implied"
 RISK_TABLE = "iv_risk"
 EXPLAIN_TABLE = "iv_explain"
 VAR_TABLE = "iv_var"
+VAR_ATTRIB_TABLE = "iv_var_attrib"
 SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
@@ -461,6 +462,11 @@ class CompleteOptimizedPipeline:
         dead_options and `backtest`: per level a dict(tp, eligible, exceedances, exceedance_rate): eligible = the snapshots with a
         finite VaR whose pair p -> p + lag has a finite net actual P&L in the P&L explain, exceedances = those whose actual P&L is
         below -VaR, exceedance_rate = their share (NaN without an eligible snapshot), to be read beside tp."""
+        return self._var_stage(book_file, lag, window, levels, min_scenarios)
+
+    def _var_stage(self, book_file, lag, window, levels, min_scenarios, each=None) -> dict:
+        """The stage behind run_var and run_varattrib: run_var's work and result; each(builder, res, held, fit, reports), when
+        given, is called once per underlying with the VarReports just made, after its iv_var table is written."""
         from iv_interpolation_amd import _lib
         from iv_interpolation_amd.engine import hsim_settings
         from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, explain_frame, var_frame
@@ -490,8 +496,11 @@ class CompleteOptimizedPipeline:
             if held.empty:                                   # no position in this underlying: no table for it
                 print(f"  {res.underlying}: no option of the book, skipped")
                 continue
-            table = var_frame(builder.var([res], held, [fit], lag=lag, window=window, tail_probs=levels, min_scenarios=min_scenarios), [res])
+            reports = builder.var([res], held, [fit], lag=lag, window=window, tail_probs=levels, min_scenarios=min_scenarios)
+            table = var_frame(reports, [res])
             self.store.write_table(VAR_TABLE, res.underlying, table)
+            if each is not None:
+                each(builder, res, held, fit, reports)
             realised = explain_frame(builder.explain([res], held, [fit], lag=lag), [res])
             both = table.merge(realised[["start", "actual"]], left_on="date", right_on="start", how="inner")
             actual = both["actual"].to_numpy(np.float64)
@@ -511,6 +520,47 @@ class CompleteOptimizedPipeline:
               + ", ".join(f"tp {b['tp']:g}: {b['exceedances']}/{b['eligible']} ({b['exceedance_rate']:.3%})" for b in backtest))
         return {"success": n_var > 0, "underlyings": len(results), "rows": n_rows, "fitted_rows": n_fit, "butterfly_rows": n_bf,
                 "var_rows": n_var, "dead_options": n_dead, "backtest": backtest, "duration": duration}
+
+    def run_varattrib(self, book_file: Optional[str] = None, lag: int = 1, window: int = 256, levels=(0.05, 0.01), min_scenarios: int = 20,
+                      group_by: str = "expiry") -> dict:
+        """VaR attribution: run_var, then the VaR and expected shortfall of every snapshot attributed to
+        the options of the book and to groups of them (group_by: "expiry" or "side") on the device: component ES = the mean of
+        the option's own P&L over the scenarios of the book's tail, component VaR = its P&L in the VaR scenario.  No level's tail
+        may exceed 64 scenarios (window x level <= 64).  One `iv_var_attrib` table per underlying (var_attribution_frame's
+        columns) besides run_var's `iv_var`.  The result has run_var's keys plus attrib_rows and top_contributors: the ten
+        options with the largest mean |component ES / ES| at the first level over the snapshots, as a list of dicts (underlying,
+        symbol, strike, expiry, callput, quantity, group, mean_abs_share, mean_ces)."""
+        from iv_interpolation_amd.engine import attrib_settings
+        from iv_interpolation_amd.snapshots import top_contributors, var_attribution_frame
+        if group_by not in ("expiry", "side"):
+            return {"success": False, "error": f"group_by {group_by!r} is neither 'expiry' nor 'side'"}
+        try:
+            attrib_settings(lag, window, levels, min_scenarios)
+        except (ValueError, TypeError) as e:
+            return {"success": False, "error": str(e)}
+        rows, tops = [0], []
+
+        def attribute(builder, res, held, fit, reports):
+            rep = builder.var_attribution([res], held, reports, [fit], lag=lag, window=window, tail_probs=levels,
+                                          min_scenarios=min_scenarios, group_by=group_by)
+            table = var_attribution_frame(rep, [res])
+            self.store.write_table(VAR_ATTRIB_TABLE, res.underlying, table)
+            rows[0] += len(table)
+            top = top_contributors(rep, [res])
+            if "symbol" in held.columns:
+                top.insert(1, "symbol", held["symbol"].to_numpy(object)[top["option"].to_numpy(np.int64)])
+            tops.append(top.drop(columns="option"))
+            print(f"  {res.underlying}: {len(table)} attribution rows in {len(rep[0].labels)} groups")
+        result = self._var_stage(book_file, lag, window, levels, min_scenarios, each=attribute)
+        if "error" in result:
+            return result
+        top = pd.concat(tops, ignore_index=True) if tops else pd.DataFrame()
+        if len(top):
+            top = top.sort_values("mean_abs_share", ascending=False, kind="stable").head(10)
+            top["expiry"] = top["expiry"].astype(str)
+        print(f"VAR ATTRIBUTION COMPLETE: {rows[0]:,} rows; largest mean |ES share|: "
+              + ", ".join(f"{t.get('symbol', t['strike'])} {t['mean_abs_share']:.1%}" for t in top.head(3).to_dict("records")))
+        return {**result, "success": result["success"] and rows[0] > 0, "attrib_rows": rows[0], "top_contributors": top.to_dict("records")}
 
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
@@ -692,12 +742,13 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "all"], default="all")
     parser.add_argument("--book", metavar="FILE", help="--task risk / explain / var: a CSV of symbol, quantity (default: every listed contract, +1 each)")
     parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain / var: the pair is snapshot p and snapshot p + N (default 1)")
     parser.add_argument("--window", type=int, default=256, metavar="W", help="--task var: scenarios kept per snapshot (default 256)")
     parser.add_argument("--levels", default="0.05,0.01", metavar="P,P", help="--task var: tail probabilities (default 0.05,0.01)")
     parser.add_argument("--min-scenarios", type=int, default=20, metavar="N", help="--task var: fewer valid scenarios than N give no VaR (default 20)")
+    parser.add_argument("--group-by", choices=["expiry", "side"], default="expiry", help="--task varattrib: the groups the VaR is attributed to (default expiry)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
     parser.add_argument("--estimate", action="store_true", help="Show estimates only")
@@ -757,6 +808,9 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
                 result = pipeline.run_explain(args.book, args.lag)
             elif args.task == "var":
                 result = pipeline.run_var(args.book, args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios)
+            elif args.task == "varattrib":
+                result = pipeline.run_varattrib(args.book, args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()],
+                                                args.min_scenarios, args.group_by)
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

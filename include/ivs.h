@@ -858,6 +858,57 @@ typedef struct ivs_hsim_args {
 int ivs_svi_hsim_f64(const ivs_hsim_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Attribution of the VaR and expected shortfall of ivs_svi_hsim_f64 to the options of the book and to groups of them (DESIGN.md
+ * section 20, rules A0-A8; additive to ABI 5): the Euler allocation of the tail.  Inputs as for ivs_svi_hsim_f64 without
+ * scen_per_wg and stages, plus pnl and scen_flags [B][window] as an ivs_svi_hsim_f64 call on the same data wrote them (INPUTS
+ * here), group [Q] (int32, device, one list for all snapshots; NULL = every option in group 0) and nG in 1..16.  An option
+ * whose group id is outside 0..nG-1 is in no group.
+ * Scenario s of snapshot p is ranked when it has no flag, its P&L is a number and it exists (s <= p - lag); the order is
+ * ascending, ties by the lower s.  n = the ranked scenarios, m_l = max(1, floor(n tp_l)) (one IEEE product); level l is active
+ * iff n >= min_scen and n > 0.  For rank r < max_l m_l with scenario s, t(q, r) = qty_q (P' - P) is the term of option q that
+ * ivs_svi_hsim_f64 added to pnl[p][s]: the same device functions in the same order, the same bits.
+ *   order [B][window] (int32)          the s of rank r for r < n, -1 after.  May be NULL.
+ *   n_tail [B][nL] (int32)             m_l, 0 for an inactive level.  Required when nL > 0.
+ *   ces [B][nL][Q]                     0.0 - (sum over r < m_l of t(q, r), added in rank order from +0.0) / m_l.  May be NULL.
+ *   cvar [B][nL][Q]                    0.0 - t(q, m_l - 1).  May be NULL.
+ *   cvar_group, ces_group [B][nL][nG]  the same with G(g, r) in place of t: the sum over the live options of group g of t(q, r),
+ *                                      formed as ivs_svi_hsim_f64 forms a scenario's P&L (no atomics, an order that depends on
+ *                                      Q alone).  With nG = 1 and group NULL they carry the bits of var and es.  Each may be NULL.
+ * A dead option has NaN in ces and cvar; an inactive level and an UNORDERED snapshot or one without a live slice have NaN
+ * everywhere; a group without a live member has +0.0.  An output left out is neither computed nor written.  Rows of pnl and
+ * scen_flags that are not those of an ivs_svi_hsim_f64 call on the same data give unspecified values but no access out of range.
+ *
+ * IVS_EINVAL and IVS_ERANGE as for ivs_svi_hsim_f64, plus IVS_ERANGE: nG outside 1..16, and a level whose largest tail
+ * max(1, floor(window tp_l)) exceeds 64 scenarios (the work grows with the tail and the per-rank group sums live in LDS; window
+ * 1024 at 5 % is 51).  B == 0, mT == 0 or Q == 0 is a no-op (nothing is written; engine.svi_hsim_attrib defines the result);
+ * the limits above are checked before that.  A refused call launches nothing and touches no buffer.  No workspace, no
+ * allocation, no synchronisation (capturable); ONE launch.
+ */
+typedef struct ivs_hsim_attrib_args {
+    const double* params; /* [B][mT][5] */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* u; const double* tau; int64_t q_stride;
+    const uint8_t* is_put; /* [Q] or NULL */
+    const double* qty;     /* [Q] */
+    int32_t strike_mode;
+    int32_t mT; int64_t Q; int64_t B;
+    int32_t lag;
+    int32_t window;            /* 1..1024 */
+    const double* tail_probs;  /* host */ int32_t nL; /* 0..8 */
+    int32_t min_scen;          /* >= 1 */
+    const double* pnl;         /* [B][window], input */
+    const int32_t* scen_flags; /* [B][window], input */
+    const int32_t* group;      /* [Q] or NULL */
+    int32_t nG;                /* 1..16 */
+    double* ces; double* cvar;             /* [B][nL][Q], each may be NULL */
+    double* ces_group; double* cvar_group; /* [B][nL][nG], each may be NULL */
+    int32_t* n_tail;           /* [B][nL] */
+    int32_t* order;            /* [B][window], may be NULL */
+} ivs_hsim_attrib_args;
+int ivs_svi_hsim_attrib_f64(const ivs_hsim_attrib_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -946,7 +997,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
  * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64,
- * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64 and ivs_svi_book_f64 set it too */
+ * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64 and ivs_svi_hsim_attrib_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

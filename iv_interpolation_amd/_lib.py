@@ -35,6 +35,7 @@ RK_MAX_SHOCKS, RK_MAX_GRID = 64, 1024
 # IVS_HS_*: per-scenario flags of the historical simulation
 HS_ABSENT, HS_VOID_PAIR, HS_NEG_VOL = 1, 2, 4
 HS_MAX_WINDOW, HS_MAX_LEVELS = 1024, 8
+HA_MAX_TAIL, HA_MAX_GROUPS = 64, 16
 # IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
@@ -205,6 +206,16 @@ class HsimArgs(C.Structure):
                 ("value", _p)]
 
 
+class HsimAttribArgs(C.Structure):
+    """ivs_hsim_attrib_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("u", _p), ("tau", _p), ("q_stride", _i64), ("is_put", _p), ("qty", _p), ("strike_mode", _i32), ("mT", _i32),
+                ("Q", _i64), ("B", _i64), ("lag", _i32), ("window", _i32),
+                ("tail_probs", C.POINTER(C.c_double)), ("nL", _i32), ("min_scen", _i32),
+                ("pnl", _p), ("scen_flags", _p), ("group", _p), ("nG", _i32),
+                ("ces", _p), ("cvar", _p), ("ces_group", _p), ("cvar_group", _p), ("n_tail", _p), ("order", _p)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -255,6 +266,7 @@ SIGNATURES = {
     "ivs_svi_book_f64": (C.c_int, [C.POINTER(BookArgs), _p, _sz, _p]),
     "ivs_svi_explain_f64": (C.c_int, [C.POINTER(ExplainArgs), _p, _sz, _p]),
     "ivs_svi_hsim_f64": (C.c_int, [C.POINTER(HsimArgs), _p, _sz, _p]),
+    "ivs_svi_hsim_attrib_f64": (C.c_int, [C.POINTER(HsimAttribArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

@@ -17,6 +17,7 @@
 #include "ivs_risk.hpp"
 #include "ivs_explain.hpp"
 #include "ivs_hsim.hpp"
+#include "ivs_hsim_attrib.hpp"
 #include "ivs_interp1d.hpp"
 #include "ivs_frame.hpp"
 #include "ivs_implied.hpp"
@@ -788,6 +789,44 @@ int ivs_svi_hsim_f64(const ivs_hsim_args* a, void*, size_t, void* stream) {
         return end_call("hsim_tail_kernel");
     }
     return IVS_OK;
+}
+
+int ivs_svi_hsim_attrib_f64(const ivs_hsim_attrib_args* a, void*, size_t, void* stream) {
+    const char* fn = "ivs_svi_hsim_attrib_f64";
+    if (int rc = begin_call(fn, a)) return rc;
+    if (a->nL < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->Q, a->tq_stride, a->q_stride, a->strike_mode)) return rc;
+    if (a->lag < 1) return fail(IVS_ERANGE, "%s: lag=%d < 1", fn, a->lag);
+    if (a->window < 1 || a->window > ivs::HS_MAX_WINDOW)
+        return fail(IVS_ERANGE, "%s: window=%d outside [1,%d]", fn, a->window, ivs::HS_MAX_WINDOW);
+    if (a->nL > ivs::HS_MAX_LEVELS) return fail(IVS_ERANGE, "%s: nL=%d > %d tail probabilities", fn, a->nL, ivs::HS_MAX_LEVELS);
+    if (a->nL > 0 && !a->tail_probs) return fail(IVS_EINVAL, "%s: null tail probabilities", fn);
+    for (int l = 0; l < a->nL; ++l)
+        if (!(a->tail_probs[l] > 0.0 && a->tail_probs[l] < 1.0))
+            return fail(IVS_ERANGE, "%s: tail probability %d (%g) is not inside (0, 1)", fn, l, a->tail_probs[l]);
+    if (a->min_scen < 1) return fail(IVS_ERANGE, "%s: min_scen=%d < 1", fn, a->min_scen);
+    if (a->nG < 1 || a->nG > ivs::HA_MAX_GROUPS) return fail(IVS_ERANGE, "%s: nG=%d outside [1,%d]", fn, a->nG, ivs::HA_MAX_GROUPS);
+    for (int l = 0; l < a->nL; ++l) {                                                              // A7, formed as H7 forms m
+        const int m = (int)__builtin_floor((double)a->window * a->tail_probs[l]);
+        if ((m < 1 ? 1 : m) > ivs::HA_MAX_TAIL)
+            return fail(IVS_ERANGE, "%s: tail probability %d (%g) of window=%d is a tail of %d > %d scenarios", fn, l, a->tail_probs[l],
+                        a->window, m, ivs::HA_MAX_TAIL);
+    }
+    if (a->B == 0 || a->mT == 0 || a->Q == 0) return IVS_OK;                                       // A8
+    if (!a->params || !a->Tq || !a->spot || !a->u || !a->tau || !a->qty || !a->pnl || !a->scen_flags || (a->nL > 0 && !a->n_tail))
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (int rc = check_query_launch(fn, "options", a->B, a->mT, a->Q, a->tq_stride, a->q_stride)) return rc;
+    if (a->B > 0x7fffffffLL / a->window)
+        return fail(IVS_ERANGE, "%s: %lld x %d scenarios exceed one launch", fn, (long long)a->B, a->window);
+    ivs::HsimAttribParams p{};
+    set_query_fields(p, a);
+    p.lag = a->lag; p.window = a->window; p.nL = a->nL; p.min_scen = a->min_scen; p.nG = a->nG;
+    for (int l = 0; l < a->nL; ++l) p.tp[l] = a->tail_probs[l];
+    p.pnl = a->pnl; p.scen_flags = a->scen_flags; p.group = a->group;
+    p.ces = a->ces; p.cvar = a->cvar; p.ces_group = a->ces_group; p.cvar_group = a->cvar_group;
+    p.n_tail = a->n_tail; p.order = a->order;
+    hipLaunchKernelGGL(ivs::svi_hsim_attrib_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
+    return end_call("svi_hsim_attrib_kernel");
 }
 
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void*, size_t, void* stream) {

@@ -794,6 +794,88 @@ def svi_hsim(params, Tq, spot, rate, u, tau, qty, *, lag: int = 1, window: int =
     return out
 
 
+ATTRIB_OUTPUTS = ("ces", "cvar", "ces_group", "cvar_group", "n_tail", "order")
+ATTRIB_OPTIONAL = ("ces", "cvar", "ces_group", "cvar_group", "order")
+
+
+def attrib_settings(lag, window, tail_probs, min_scen, n_groups=1):
+    """The host-side checks of a VaR attribution: those of hsim_settings, 1..16 groups, and rule A7: no
+    level's largest tail max(1, floor(window x tp)) may exceed 64 scenarios; ValueError otherwise.  Returns (lag, window,
+    tail_probs as a list, min_scen, n_groups)."""
+    import math
+    lag, window, tp, min_scen, _ = hsim_settings(lag, window, tail_probs, min_scen)
+    if int(n_groups) != n_groups or not 1 <= n_groups <= _lib.HA_MAX_GROUPS:
+        raise ValueError(f"n_groups {n_groups!r} is not an integer in 1..{_lib.HA_MAX_GROUPS}")
+    for x in tp:
+        if max(1, math.floor(float(window) * x)) > _lib.HA_MAX_TAIL:
+            raise ValueError(f"tail probability {x!r} of a window of {window} is a tail of {math.floor(float(window) * x)} scenarios: "
+                             f"at most {_lib.HA_MAX_TAIL} are supported")
+    return lag, window, tp, min_scen, int(n_groups)
+
+
+def svi_hsim_attrib(params, Tq, spot, rate, u, tau, qty, pnl, scen_flags, *, group=None, n_groups: int = 1, lag: int = 1,
+                    window: int = 256, tail_probs=DEFAULT_TAIL_PROBS, min_scen: int = 20, is_put=None, strike_mode: int = 0,
+                    want=ATTRIB_OPTIONAL, out=None, stream=None):
+    """The VaR and expected shortfall of svi_hsim attributed to the options of the book and to groups of them
+    (ivs_svi_hsim_attrib_f64; rules A0-A8 of DESIGN.md section 20): component ES of an option is the mean of its own P&L over
+    the scenarios of the book's tail, component VaR its P&L in the VaR scenario; summed over the book they give es and var back.
+    Inputs as in svi_hsim, plus pnl float64 and scen_flags int32 [B,window] as svi_hsim returned them for the same inputs and
+    settings, group int32 [Q] (one list for all snapshots; None = every option in group 0; an id outside 0..n_groups-1 is in no
+    group) and n_groups in 1..16.  attrib_settings has the limits.
+    want: which of ces, cvar [B,nL,Q], ces_group, cvar_group [B,nL,n_groups] and order [B,window] to compute; one left out is
+    neither computed nor written (None in the result).  n_tail int32 [B,nL] (the size of every tail, 0 for an inactive level)
+    is always given.  `out`: optional dict of preallocated outputs.
+    The C call writes nothing when mT == 0 or Q == 0; the wrapper then fills the result itself: without a slice every snapshot
+    is degenerate (NaN everywhere, n_tail 0), and a book without options has +0.0 in the groups of every active level; order and
+    n_tail are then formed from pnl and scen_flags by rule A1.
+    Returns dict(ces, cvar, ces_group, cvar_group, n_tail, order) of device tensors."""
+    _check_strike_mode(strike_mode)
+    want = _wanted(want, ATTRIB_OPTIONAL)
+    lag, window, tp, min_scen, nG = attrib_settings(lag, window, tail_probs, min_scen, n_groups)
+    nL = len(tp)
+    torch = require_device()
+    B, Q0 = _svi_inputs(torch, params, Tq, spot)[3], u.shape[-1]
+    pnl = _f64(torch, pnl, "pnl")
+    if not scen_flags.is_cuda or scen_flags.dtype != torch.int32:
+        raise TypeError("scen_flags must be a CUDA int32 tensor")
+    scen_flags = scen_flags.contiguous()
+    if tuple(pnl.shape) != (B, window) or tuple(scen_flags.shape) != (B, window):
+        raise ValueError(f"pnl and scen_flags must be [B, window] = {(B, window)}")
+    if group is not None:
+        if not group.is_cuda or group.dtype != torch.int32:
+            raise TypeError("group must be a CUDA int32 tensor")
+        if tuple(group.shape) != (Q0,):
+            raise ValueError("group must be [Q]: one group id per option, shared by all snapshots")
+        group = group.contiguous()
+
+    def shapes(torch, B, Q):
+        i32, f64 = torch.int32, torch.float64
+        return {"ces": ((B, nL, Q), f64, "ces" in want), "cvar": ((B, nL, Q), f64, "cvar" in want),
+                "ces_group": ((B, nL, nG), f64, "ces_group" in want), "cvar_group": ((B, nL, nG), f64, "cvar_group" in want),
+                "n_tail": ((B, nL), i32, True), "order": ((B, window), i32, "order" in want)}
+    torch, out, B, mT, Q = _option_call(
+        "ivs_svi_hsim_attrib_f64", _lib.HsimAttribArgs(), params, Tq, spot, rate, u, tau, strike_mode, out, stream, shapes, is_put, qty,
+        lag=lag, window=window, tail_probs=_doubles(tp), nL=nL, min_scen=min_scen, pnl=_ptr(pnl), scen_flags=_ptr(scen_flags),
+        group=_ptr(group), nG=nG)
+    _hold_for_stream(torch, stream, pnl, scen_flags, group)
+
+    def empty():                                             # A8
+        nan, device = float("nan"), pnl.device
+        n_p = (torch.arange(B, device=device) - lag + 1).clamp(0, window)
+        ranked = (scen_flags == 0) & ~torch.isnan(pnl) & (torch.arange(window, device=device)[None, :] < n_p[:, None]) & (mT > 0)
+        n = ranked.sum(dim=1)
+        idx = torch.sort(torch.where(ranked, pnl, float("inf")), dim=1, stable=True).indices
+        order = torch.where(torch.arange(window, device=device)[None, :] < n[:, None], idx, -1).to(torch.int32)
+        m = torch.floor(n.to(torch.float64)[:, None] * torch.tensor(tp, dtype=torch.float64, device=device)[None, :]).clamp(min=1)
+        on = ((n >= min_scen) & (n > 0))[:, None].expand(B, nL)
+        sums = torch.where(on, 0.0, nan)[:, :, None].expand(B, nL, nG)
+        return {"ces": nan, "cvar": nan, "ces_group": sums, "cvar_group": sums, "n_tail": torch.where(on, m, 0.0).to(torch.int32),
+                "order": order}
+    if B > 0 and (mT == 0 or Q == 0):
+        _fill(torch, stream, out, empty)
+    return out
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

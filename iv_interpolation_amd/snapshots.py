@@ -281,6 +281,32 @@ class VarReport:
     value: object                    # [B, 2] sums of quantity x price and |quantity| x price
 
 
+@dataclass
+class VarAttributionReport:
+    """One underlying's VaR and expected shortfall attributed to the options of the book and to groups of them (rules A0-A8).
+    The value arrays are device tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    lag: int
+    window: int
+    tail_probs: np.ndarray           # [nL]
+    min_scenarios: int
+    strikes: np.ndarray              # [Q]
+    expiries: pd.DatetimeIndex       # [Q]
+    is_put: np.ndarray               # [Q] bool
+    quantity: np.ndarray             # [Q]
+    group: np.ndarray                # [Q] int32: the option's group, -1 = in none
+    labels: List[str]                # [nG] the groups' names
+    ces: object                      # [B, nL, Q] component ES: sums to es over the live options
+    cvar: object                     # [B, nL, Q] component VaR: sums to var
+    ces_group: object                # [B, nL, nG]
+    cvar_group: object               # [B, nL, nG]
+    n_tail: object                   # [B, nL] int32: the scenarios in the tail, 0 = no VaR at this level
+    order: object                    # [B, window] int32: the scenario of every rank, -1 past the ranked ones
+    var: object                      # [B, nL] the VarReport's
+    es: object                       # [B, nL]
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -355,6 +381,14 @@ class HipBackend:
         d = lambda a: self._up(a, np.float64)  # noqa: E731
         return engine.svi_hsim(params, d(Tq), spot, rate, d(u), d(tau), d(qty), lag=lag, window=window, tail_probs=tail_probs,
                                min_scen=min_scen, is_put=self._up(is_put, np.uint8), strike_mode=strike_mode, stream=self.stream)
+
+
+    def hsim_attrib(self, params, Tq, spot, rate, u, tau, qty, pnl, scen_flags, group, n_groups, lag, window, tail_probs, min_scen,
+                    is_put, strike_mode):
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
+        return engine.svi_hsim_attrib(params, d(Tq), spot, rate, d(u), d(tau), d(qty), pnl, scen_flags, group=self._up(group, np.int32),
+                                      n_groups=n_groups, lag=lag, window=window, tail_probs=tail_probs, min_scen=min_scen,
+                                      is_put=self._up(is_put, np.uint8), strike_mode=strike_mode, stream=self.stream)
 
 
 def _host(a):
@@ -721,6 +755,66 @@ class SnapshotSurfaceBuilder:
             reports.append(VarReport(r.underlying, r.dates, lag, window, np.asarray(tp, np.float64), min_scenarios, strikes, expiry, is_put,
                                      qty, tau, float(rate), h["pnl"], h["scen_flags"], h["var"], h["es"], h["n_valid"], h["n_dead"],
                                      h["worst"], h["value"]))
+        return reports
+
+    # ------------------------------------------------------------------ var attribution
+    @staticmethod
+    def _groups(book: pd.DataFrame, expiry: pd.DatetimeIndex, is_put: np.ndarray, group_by, groups):
+        """The group id [Q] (int32, -1 = in no group) and the labels of var_attribution()."""
+        from ._lib import HA_MAX_GROUPS
+        if groups is not None:
+            if "symbol" not in book.columns:
+                raise KeyError("symbol")
+            lab = book["symbol"].map(pd.Series(groups))
+            labels = sorted(lab.dropna().astype(str).unique())
+            if not 1 <= len(labels) <= HA_MAX_GROUPS:
+                raise ValueError(f"groups names {len(labels)} labels: 1 to {HA_MAX_GROUPS} are supported")
+            ids = lab.astype(object).map(lambda x: labels.index(str(x)) if pd.notna(x) else -1)
+            return ids.to_numpy(np.int32), labels
+        if group_by == "side":
+            return is_put.astype(np.int32), ["call", "put"]
+        if group_by != "expiry":
+            raise ValueError(f"group_by {group_by!r} is neither 'expiry' nor 'side'")
+        uniq = expiry.dropna().unique().sort_values()
+        if len(uniq) > HA_MAX_GROUPS:                            # the 15 nearest, then one group for the rest
+            uniq = uniq[:HA_MAX_GROUPS - 1]
+        labels = [str(e) for e in uniq] or ["none"]
+        ids = uniq.get_indexer(expiry)
+        if len(labels) == HA_MAX_GROUPS - 1 and (np.asarray(~expiry.isna()) & (ids < 0)).any():
+            labels.append("later")
+            ids = np.where(np.asarray(~expiry.isna()) & (ids < 0), HA_MAX_GROUPS - 1, ids)
+        return ids.astype(np.int32), labels
+
+    def var_attribution(self, results: Sequence[SnapshotSurfaces], book: pd.DataFrame, var_reports=None, svi_reports=None,
+                        rate: float = 0.0, lag: int = 1, window: int = 256, tail_probs=(0.05, 0.01), min_scenarios: int = 20,
+                        rounds: int = 0, group_by: str = "expiry", groups=None) -> List["VarAttributionReport"]:
+        """The VaR and expected shortfall of var() attributed to the options of the book and to groups of them (rules A0-A8):
+        one VarAttributionReport per underlying.  Component ES of an option is the mean of its own P&L over the scenarios of the
+        book's tail, component VaR its P&L in the VaR scenario; both sum to the book's figure.  var_reports: the VarReports of
+        var(results, book, ...) with the same rate and settings; None runs var() first.  group_by: "expiry" (one group per
+        expiry; with more than 16 the 15 nearest and `later`) or "side" (call, put); groups: instead a symbol -> label Series
+        of at most 16 labels, read against the book's symbol column (an option without a label is in no group).  No level's
+        tail may exceed 64 scenarios: max(1, floor(window x tail probability)) <= 64.  svi_reports as for calendar()."""
+        from .engine import attrib_settings
+        svi_reports, strikes, expiry, is_put, qty, (lag, window, tp, min_scenarios, _) = self._book(
+            book, (results, svi_reports, rate, rounds), settings=lambda: attrib_settings(lag, window, tail_probs, min_scenarios))
+        if var_reports is None:
+            var_reports = self.var(results, book, svi_reports, rate, lag, window, tp, min_scenarios)
+        if len(var_reports) != len(results):
+            raise ValueError(f"{len(var_reports)} VaR reports for {len(results)} surfaces")
+        group, labels = self._groups(book, expiry, is_put, group_by, groups)
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v, h in zip(results, svi_reports, var_reports):
+            if (h.lag, h.window, h.min_scenarios) != (lag, window, min_scenarios) or list(h.tail_probs) != list(tp):
+                raise ValueError("the VaR reports were made with other settings (lag, window, tail_probs, min_scenarios)")
+            tau = self._tau(expiry, r.dates)
+            u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
+            a = be.hsim_attrib(v.params, r.tenors, r.spot, float(rate), u, tau, qty, h.pnl, h.scen_flags, group, len(labels), lag,
+                               window, tp, min_scenarios, is_put, 1)
+            reports.append(VarAttributionReport(r.underlying, r.dates, lag, window, np.asarray(tp, np.float64), min_scenarios, strikes,
+                                                expiry, is_put, qty, group, labels, a["ces"], a["cvar"], a["ces_group"], a["cvar_group"],
+                                                a["n_tail"], a["order"], h.var, h.es))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -1264,3 +1358,61 @@ def var_frame(reports: Sequence[VarReport], snapshots: Sequence[SnapshotSurfaces
                              "worst_pnl": f64, "worst_start": ns, "value": f64, "gross": f64, "n_dead": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def var_attribution_frame(reports: Sequence[VarAttributionReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per snapshot with quotes > 0, tail probability and group, ordered by (underlying, date, level, group): columns
+    underlying, date, level (the tail probability), group (its label), ces and cvar (the group's component ES and VaR; losses
+    are positive), ces_share (ces / es of the book), n_tail (the scenarios in the tail, 0 = no VaR at this level) and var_start
+    (the first snapshot of the VaR scenario's pair; NaT without one)."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        nL, nG = len(p.tail_probs), len(p.labels)
+        ces, cvar = _host(p.ces_group)[keep], _host(p.cvar_group)[keep]                    # [n, nL, nG]
+        es, n_tail, order = _host(p.es)[keep], _host(p.n_tail)[keep].astype(np.int64), _host(p.order)[keep].astype(np.int64)
+        has = n_tail > 0
+        s = np.take_along_axis(order, np.maximum(n_tail - 1, 0), axis=1) if len(keep) and nL else np.zeros((len(keep), nL), np.int64)
+        start = np.where(has, keep[:, None] - p.lag - s, 0)                                 # H0
+        when = pd.DatetimeIndex(p.dates[start.ravel()]).where(has.ravel()) if start.size else p.dates[:0]
+        with np.errstate(all="ignore"):
+            share = ces / es[:, :, None]
+        shape = (len(keep), nL, nG)
+        rep = lambda a: np.broadcast_to(a, shape).ravel()  # noqa: E731
+        parts.append(pd.DataFrame({
+            "underlying": p.underlying, "date": p.dates[keep].repeat(nL * nG),
+            "level": rep(np.asarray(p.tail_probs, np.float64)[None, :, None]),
+            "group": np.asarray(p.labels, object)[rep(np.arange(nG)[None, None, :])] if nG else np.zeros(0, object),
+            "ces": ces.ravel(), "cvar": cvar.ravel(), "ces_share": share.ravel(),
+            "n_tail": rep(n_tail[:, :, None]).astype(np.int32), "var_start": when.repeat(nG)}))
+    if not parts:
+        f64, ns = pd.Series(dtype=np.float64), pd.Series(dtype="datetime64[ns]")
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": ns, "level": f64, "group": pd.Series(dtype=object),
+                             "ces": f64, "cvar": f64, "ces_share": f64, "n_tail": pd.Series(dtype=np.int32), "var_start": ns})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def top_contributors(reports: Sequence[VarAttributionReport], snapshots: Sequence[SnapshotSurfaces], level: int = 0, count: int = 10) -> pd.DataFrame:
+    """The `count` options with the largest mean |ces / es| over the snapshots with quotes > 0 and a VaR at tail probability
+    number `level`: columns underlying, option (its row in the book), strike, expiry, callput, quantity, group, mean_abs_share,
+    mean_ces."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        if not len(p.tail_probs) or not len(keep) or not len(p.strikes):
+            continue
+        ces, es = _host(p.ces)[keep, level], _host(p.es)[keep, level]                       # [n, Q], [n]
+        with np.errstate(all="ignore"):
+            share = np.abs(ces / es[:, None])
+            seen = np.isfinite(share)
+            mean = np.where(seen.any(axis=0), np.where(seen, share, 0.0).sum(axis=0) / np.maximum(seen.sum(axis=0), 1), np.nan)
+            mces = np.where(seen.any(axis=0), np.where(seen, ces, 0.0).sum(axis=0) / np.maximum(seen.sum(axis=0), 1), np.nan)
+        lab = np.asarray(list(p.labels) + [""], object)[p.group]
+        parts.append(pd.DataFrame({"underlying": p.underlying, "option": np.arange(len(p.strikes)), "strike": p.strikes, "expiry": p.expiries,
+                                   "callput": np.where(p.is_put, "P", "C"), "quantity": p.quantity, "group": lab,
+                                   "mean_abs_share": mean, "mean_ces": mces}))
+    if not parts:
+        return pd.DataFrame(columns=["underlying", "option", "strike", "expiry", "callput", "quantity", "group", "mean_abs_share", "mean_ces"])
+    df = pd.concat(parts, ignore_index=True).dropna(subset=["mean_abs_share"])
+    return df.sort_values("mean_abs_share", ascending=False, kind="stable").head(count).reset_index(drop=True)
