@@ -1,139 +1,35 @@
-// extern "C" entry points of libivs.so (declared in include/ivs.h).
+// Unit of libivs.so: the snapshot analytics (snapshot, smile, arbitrage, moments, SVI, SSVI, distribution, calendar,
+// evaluation, the book family), the Black-Scholes calls, candles and the bridge.
 // Argument validation happens here on the host; kernels assume validated shapes.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <type_traits>
 
-#include "../../include/ivs.h"
 #include "ivs_arbitrage.hpp"
 #include "ivs_bridge.hpp"
 #include "ivs_candles.hpp"
+#include "ivs_dispatch.hpp"
 #include "ivs_distribution.hpp"
-#include "ivs_svi_surface.hpp"
-#include "ivs_risk.hpp"
 #include "ivs_explain.hpp"
+#include "ivs_greeks.hpp"
+#include "ivs_host.hpp"
 #include "ivs_hsim.hpp"
 #include "ivs_hsim_attrib.hpp"
-#include "ivs_interp1d.hpp"
-#include "ivs_frame.hpp"
 #include "ivs_implied.hpp"
 #include "ivs_moments.hpp"
+#include "ivs_risk.hpp"
 #include "ivs_smile.hpp"
 #include "ivs_snapshot.hpp"
-#include "ivs_svi.hpp"
 #include "ivs_ssvi.hpp"
-#include "ivs_surface_dense.hpp"
-#include "ivs_surface_dense_var2.hpp"
-#include "ivs_surface_pass.hpp"
-#include "ivs_surface_generic.hpp"
+#include "ivs_svi.hpp"
+#include "ivs_svi_surface.hpp"
+
+using namespace ivs::host;
 
 namespace {
 
-thread_local char g_err[512] = "";
-thread_local const char* g_last_kernel = "";
-thread_local char g_kernel_name[64] = "";             // ivs_last_kernel() of the surface fast paths: family<method>
-// diagnostics (ivs_debug_stamps): per calling thread, like the error string
-thread_local unsigned long long* g_stamp_buf = nullptr;   // device buffer for the diagnostic (stamped) dense kernel
-thread_local int64_t g_stamp_cap = 0;
-thread_local int64_t g_last_grid = 0;
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(IVS_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
-    return IVS_OK;
-}
-
-// family<method>; a family that already carries its argument ("surface_dense_kernel<stamp>") is reported as it is
-void set_last_kernel(const char* family, int method) {
-    if (strchr(family, '<')) snprintf(g_kernel_name, sizeof(g_kernel_name), "%s", family);
-    else snprintf(g_kernel_name, sizeof(g_kernel_name), "%s<%s>", family, ivs::method_name(method));
-    g_last_kernel = g_kernel_name;
-}
-
-bool valid_method(int m) { return m >= IVS_LINEAR && m <= IVS_BFILL; }
-
-// CU count of the CURRENT device, cached per device index (a process may drive several devices)
-std::atomic<int> g_cu[ivs::IVS_MAX_DEV];
-void current_device(int& dev, int& cus) {
-    dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    const bool cached = dev >= 0 && dev < ivs::IVS_MAX_DEV;
-    cus = cached ? g_cu[dev].load(std::memory_order_relaxed) : 0;
-    if (cus <= 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); v = 0; }
-        cus = v > 0 ? v : 256;
-        if (cached) g_cu[dev].store(cus, std::memory_order_relaxed);
-    }
-}
-int num_cu() { int d, c; current_device(d, c); return c; }
-
-// ---- the checks and launch steps the snapshot-analytics calls (ivs_*_args) share; each returns IVS_OK or the failure
-
-// opens a call: no error, no kernel yet.  None of these calls takes device scratch, so their workspace arguments go unnamed.
-int begin_call(const char* fn, const void* args) {
-    g_err[0] = 0;
-    g_last_kernel = "";
-    return args ? IVS_OK : fail(IVS_EINVAL, "%s: null args", fn);
-}
-
-// closes a call after its one launch
-int end_call(const char* kernel) {
-    g_last_kernel = kernel;
-    return check_launch(kernel);
-}
-
-// a query grid is shared by all surfaces (stride 0) or dense per surface (stride = its length)
-int check_grid_stride(const char* fn, int64_t stride, int64_t len) {
-    return stride == 0 || stride == len ? IVS_OK : fail(IVS_EINVAL, "%s: grid stride is neither 0 nor the grid's length", fn);
-}
-
-// B x mT rows are indexed, and spread over a grid, as int32
-int check_rows(const char* fn, int64_t B, int32_t mT) {
-    return B > 0x7fffffffLL / mT ? fail(IVS_ERANGE, "%s: %lld x %d rows exceed one launch", fn, (long long)B, mT) : IVS_OK;
-}
-
-// rows per wavefront of the kernels whose inversion phase packs several rows into one wavefront: fill its 64 lanes (`cap`
-// rows do), but keep ~16 wavefronts per CU while the batch is small; `forced` > 0 is the tuning / testing override
-int32_t rows_per_wave(int64_t rows, int cap, int forced) {
-    int dev, cus;
-    current_device(dev, cus);
-    int64_t group = rows / ((int64_t)cus * 16);
-    group = group < 1 ? 1 : (group > cap ? cap : group);
-    return (int32_t)(forced > 0 ? forced : group);
-}
-
-// ivs_svi_eval_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64: the shape of B snapshots of mT slices and Q queries / options each
-int check_query_shape(const char* fn, int64_t B, int32_t mT, int64_t Q, int64_t tq_stride, int64_t q_stride, int32_t strike_mode) {
-    if (B < 0 || mT < 0 || Q < 0 || tq_stride < 0 || q_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
-    if (strike_mode != 0 && strike_mode != 1) return fail(IVS_EINVAL, "%s: strike_mode=%d is neither 0 nor 1", fn, strike_mode);
-    if (mT > ivs::ST_MAX_T) return fail(IVS_ERANGE, "%s: mT=%d > %d tenors of one snapshot", fn, mT, ivs::ST_MAX_T);
-    return IVS_OK;
-}
-
-// ... and, for a batch that is not empty, their strides and launch limits; `noun` is what the call names its Q entries
-int check_query_launch(const char* fn, const char* noun, int64_t B, int32_t mT, int64_t Q, int64_t tq_stride, int64_t q_stride) {
-    if ((tq_stride != 0 && tq_stride != mT) || (q_stride != 0 && q_stride != Q))
-        return fail(IVS_EINVAL, "%s: grid or query stride is neither 0 nor the full length", fn);
-    if (int rc = check_rows(fn, B, mT)) return rc;
-    if (B > 0x7fffffffLL / Q) return fail(IVS_ERANGE, "%s: %lld x %lld %s exceed one launch", fn, (long long)B, (long long)Q, noun);
-    return IVS_OK;
-}
-
-// ... and what their kernels' params take over from the args field for field: the names agree; svi_eval has no sides, and
-// neither it nor svi_greeks has quantities
+// what the kernels' params of ivs_svi_eval_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64 and the hsim calls take
+// over from the args field for field: the names agree; svi_eval has no sides, and neither it nor svi_greeks has quantities
 template <class P, class A>
 void set_query_fields(P& p, const A* a) {
     p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.u = a->u; p.tau = a->tau;
@@ -143,269 +39,9 @@ void set_query_fields(P& p, const A* a) {
     if constexpr (!std::is_same_v<P, ivs::EvalParams> && !std::is_same_v<P, ivs::RiskParams>) p.qty = a->qty;
 }
 
-// items (scenario cells, scenarios) per workgroup of the kernels that split the n >= 1 items of each of B snapshots into runs:
-// all n, or the fewest runs of at most `cap`, while the snapshots alone give every CU `per_cu` workgroups, shorter runs below
-// that; `forced` > 0 is the tuning / testing override.  The sums of an item do not depend on the split.
-int items_per_wg(int64_t B, int n, int per_cu, int cap, int forced) {
-    int dev, cus;
-    current_device(dev, cus);
-    int64_t need = (per_cu * (int64_t)cus + B - 1) / B;
-    const int least = (n + cap - 1) / cap;
-    need = need < least ? least : (need > n ? n : need);
-    return forced > 0 ? forced : (int)((n + need - 1) / need);
-}
-
 }  // namespace
 
 extern "C" {
-
-int ivs_version(void) { return IVS_ABI_VERSION; }
-
-const char* ivs_last_error(void) { return g_err; }
-
-const char* ivs_last_kernel(void) { return g_last_kernel; }
-
-int ivs_debug_stamps(void* device_buf, int64_t n_u64) {
-    g_stamp_buf = static_cast<unsigned long long*>(device_buf);
-    g_stamp_cap = device_buf ? n_u64 : 0;
-    return (int)ivs::D_NSTAMP;
-}
-
-int64_t ivs_debug_last_grid(void) { return g_last_grid; }
-int64_t ivs_debug_mode_offset(void) { return (int64_t)offsetof(ivs::TqShared, mode); }
-
-int ivs_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return n;
-}
-
-size_t ivs_interp1d_workspace_bytes(int64_t total_knots, int64_t n_series, int32_t n_channels) {
-    if (total_knots < 0 || n_series < 0 || n_channels < 0) return 0;
-    return ivs::interp1d_ws_bytes(total_knots, n_series, n_channels);
-}
-
-namespace {
-int interp1d_impl(const char* fn, const double* xk, const double* yk, int64_t yk_stride, const int64_t* knot_off,
-                  int64_t n_series, int32_t n_channels, int64_t total_knots, const double* xq, const int64_t* q_off,
-                  int64_t total_queries, double* out, int64_t out_stride, int32_t* status, int32_t method, void* workspace,
-                  size_t workspace_bytes, void* stream, ivs::Interp1dParams& p) {
-    g_err[0] = 0;
-    if (!valid_method(method)) return fail(IVS_EINVAL, "%s: unknown method %d", fn, method);
-    if (n_series < 0 || n_channels < 0 || total_knots < 0 || total_queries < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
-    if (n_series == 0 || n_channels == 0) return IVS_OK;
-    if (!knot_off || !q_off || !status) return fail(IVS_EINVAL, "%s: null offsets/status", fn);
-    if (total_knots > 0 && (!xk || !yk)) return fail(IVS_EINVAL, "%s: null knots", fn);
-    if (total_queries > 0 && !out) return fail(IVS_EINVAL, "%s: null out", fn);
-    if (yk_stride < total_knots || out_stride < total_queries)
-        return fail(IVS_EINVAL, "%s: channel stride smaller than row length", fn);
-    if (n_series * (int64_t)n_channels > 0x7fffffffLL || (total_queries + 255) / 256 > 0x7fffffffLL)
-        return fail(IVS_ERANGE, "%s: batch too large for one launch", fn);
-    size_t need = ivs::interp1d_ws_bytes(total_knots, n_series, n_channels);
-    if (!workspace || workspace_bytes < need) return fail(IVS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
-    p.xk = xk; p.yk = yk; p.yk_stride = yk_stride; p.knot_off = knot_off;
-    p.S = n_series; p.C = n_channels; p.total_knots = total_knots;
-    p.xq = xq; p.q_off = q_off; p.total_q = total_queries;
-    p.out = out; p.out_stride = out_stride; p.status = status; p.method = method;
-    double* w = static_cast<double*>(workspace);
-    size_t plane = (size_t)n_channels * (size_t)total_knots;
-    p.wx = w; p.wy = w + plane; p.ws = w + 2 * plane; p.wcp = w + 3 * plane;
-    p.wn = reinterpret_cast<int32_t*>(w + 4 * plane);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(ivs::interp1d_prepare_kernel, dim3((unsigned)(n_series * n_channels)), dim3(256), 0, st, p);
-    int rc = check_launch("interp1d_prepare_kernel");
-    if (rc) return rc;
-    if (total_queries > 0) {
-        hipLaunchKernelGGL(ivs::interp1d_eval_kernel, dim3((unsigned)((total_queries + ivs::E1_ROWS - 1) / ivs::E1_ROWS)), dim3(256), 0, st, p);
-        rc = check_launch("interp1d_eval_kernel");
-    }
-    return rc;
-}
-}  // namespace
-
-int ivs_interp1d_batch_f64(const double* xk, const double* yk, int64_t yk_stride, const int64_t* knot_off,
-                           int64_t n_series, int32_t n_channels, int64_t total_knots,
-                           const double* xq, const int64_t* q_off, int64_t total_queries,
-                           double* out, int64_t out_stride, int32_t* status, int32_t method,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-    ivs::Interp1dParams p{};
-    p.greeks = nullptr;
-    return interp1d_impl("ivs_interp1d_batch_f64", xk, yk, yk_stride, knot_off, n_series, n_channels, total_knots, xq, q_off,
-                         total_queries, out, out_stride, status, method, workspace, workspace_bytes, stream, p);
-}
-
-int ivs_interp1d_greeks_batch_f64(const double* xk, const double* yk, int64_t yk_stride, const int64_t* knot_off,
-                                  int64_t n_series, int32_t n_channels, int64_t total_knots,
-                                  const double* xq, const int64_t* q_off, int64_t total_queries,
-                                  double* out, int64_t out_stride, int32_t* status, int32_t method,
-                                  int32_t ch_iv, int32_t ch_underlying, int32_t ch_ttm,
-                                  const int32_t* fill_idx, int64_t fill_stride, int32_t row_strike, int32_t row_rate,
-                                  int32_t row_callput, const double* strike_src, const double* rate_src,
-                                  const uint8_t* is_put_src, double* greeks, int64_t greeks_stride,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "ivs_interp1d_greeks_batch_f64";
-    g_err[0] = 0;
-    if (n_series > 0 && n_channels > 0 && total_queries > 0) {
-        if (!greeks || greeks_stride < total_queries) return fail(IVS_EINVAL, "%s: null / short greeks output", fn);
-        if (ch_iv < 0 || ch_iv >= n_channels || ch_underlying < 0 || ch_underlying >= n_channels || ch_ttm < 0 || ch_ttm >= n_channels)
-            return fail(IVS_EINVAL, "%s: channel numbers outside [0, %d)", fn, n_channels);
-        if ((row_strike >= 0 || row_rate >= 0 || row_callput >= 0) && (!fill_idx || fill_stride < total_queries))
-            return fail(IVS_EINVAL, "%s: null / short fill index", fn);
-        if ((row_strike >= 0 && !strike_src) || (row_rate >= 0 && !rate_src) || (row_callput >= 0 && !is_put_src))
-            return fail(IVS_EINVAL, "%s: a present column needs its source array", fn);
-    }
-    ivs::Interp1dParams p{};
-    p.fidx = fill_idx; p.fidx_stride = fill_stride; p.fi_strike = row_strike; p.fi_rate = row_rate; p.fi_put = row_callput;
-    p.strike_src = strike_src; p.rate_src = rate_src; p.put_src = is_put_src;
-    p.ch_iv = ch_iv; p.ch_S = ch_underlying; p.ch_T = ch_ttm;
-    p.greeks = greeks; p.greeks_stride = greeks_stride;
-    return interp1d_impl(fn, xk, yk, yk_stride, knot_off, n_series, n_channels, total_knots, xq, q_off, total_queries, out,
-                         out_stride, status, method, workspace, workspace_bytes, stream, p);
-}
-
-int ivs_ffill_index_batch(const int64_t* src_pos, const int64_t* src_off, const uint8_t* valid, int64_t valid_stride,
-                          int32_t n_cols, const int64_t* q_off, int64_t n_series, int64_t total_queries,
-                          int32_t* idx_out, int64_t out_stride, void* stream) {
-    g_err[0] = 0;
-    if (n_cols < 0 || n_series < 0 || total_queries < 0) return fail(IVS_EINVAL, "ivs_ffill_index_batch: negative size");
-    if (n_cols == 0 || n_series == 0 || total_queries == 0) return IVS_OK;
-    if (!src_pos || !src_off || !valid || !q_off || !idx_out) return fail(IVS_EINVAL, "ivs_ffill_index_batch: null pointer");
-    if (out_stride < total_queries) return fail(IVS_EINVAL, "ivs_ffill_index_batch: out_stride < total_queries");
-    if ((total_queries + 255) / 256 > 0x7fffffffLL) return fail(IVS_ERANGE, "ivs_ffill_index_batch: too many rows");
-    if (valid_stride > 0x7fffffffLL) return fail(IVS_ERANGE, "ivs_ffill_index_batch: %lld source rows exceed the int32 gather index", (long long)valid_stride);
-    ivs::FfillParams p{src_pos, src_off, valid, valid_stride, n_cols, q_off, n_series, total_queries, idx_out, out_stride};
-    hipLaunchKernelGGL(ivs::ffill_index_kernel, dim3((unsigned)((total_queries + ivs::F1_ROWS - 1) / ivs::F1_ROWS)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), p);
-    return check_launch("ffill_index_kernel");
-}
-
-extern "C++" {
-namespace {
-template <class T>
-int gather_impl(const char* fn, const void* src, int64_t src_stride, const int32_t* idx, int64_t idx_stride, const int32_t* idx_row,
-                int32_t n_cols, int64_t n, void* out, int64_t out_stride, T missing, void* stream) {
-    g_err[0] = 0;
-    if (n_cols < 0 || n < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
-    if (n_cols == 0 || n == 0) return IVS_OK;
-    if (!src || !idx || !idx_row || !out) return fail(IVS_EINVAL, "%s: null pointer", fn);
-    if (idx_stride < n || out_stride < n) return fail(IVS_EINVAL, "%s: stride smaller than row count", fn);
-    if (src_stride > 0x7fffffffLL) return fail(IVS_ERANGE, "%s: %lld source rows exceed the int32 gather index", fn, (long long)src_stride);
-    ivs::GatherParams p{src, src_stride, idx, idx_stride, idx_row, n_cols, n, out, out_stride};
-    hipLaunchKernelGGL(ivs::gather_rows_kernel<T>, dim3((unsigned)ivs::capped_blocks(n, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p, missing);
-    return check_launch(fn);
-}
-}  // namespace
-}  // extern "C++"
-
-int ivs_gather_rows_f64(const double* src, int64_t src_stride, const int32_t* idx, int64_t idx_stride, const int32_t* idx_row,
-                        int32_t n_cols, int64_t n, double* out, int64_t out_stride, void* stream) {
-    return gather_impl<double>("ivs_gather_rows_f64", src, src_stride, idx, idx_stride, idx_row, n_cols, n, out, out_stride,
-                               __builtin_nan(""), stream);
-}
-
-int ivs_gather_rows_i32(const int32_t* src, int64_t src_stride, const int32_t* idx, int64_t idx_stride, const int32_t* idx_row,
-                        int32_t n_cols, int64_t n, int32_t* out, int64_t out_stride, void* stream) {
-    return gather_impl<int32_t>("ivs_gather_rows_i32", src, src_stride, idx, idx_stride, idx_row, n_cols, n, out, out_stride,
-                                (int32_t)-1, stream);
-}
-
-int ivs_frame_rows(const int64_t* q_off, int64_t n_series, int64_t total_queries, const int64_t* first_ns,
-                   const double* chan, int64_t chan_stride, int32_t n_channels, const int32_t* sym_code,
-                   const int32_t* status, const uint8_t* needs, int64_t* date_ns, uint8_t* keep, void* stream) {
-    g_err[0] = 0;
-    if (n_series < 0 || total_queries < 0 || n_channels < 0) return fail(IVS_EINVAL, "ivs_frame_rows: negative size");
-    if (n_series == 0 || total_queries == 0) return IVS_OK;
-    if (!q_off || !first_ns || !date_ns || !keep || (n_channels > 0 && (!chan || !status || !needs)))
-        return fail(IVS_EINVAL, "ivs_frame_rows: null pointer");
-    if (chan_stride < total_queries) return fail(IVS_EINVAL, "ivs_frame_rows: chan_stride < total_queries");
-    ivs::FrameRowsParams p{q_off, n_series, total_queries, first_ns, chan, chan_stride, n_channels, sym_code, status, needs, date_ns, keep};
-    hipLaunchKernelGGL(ivs::frame_rows_kernel, dim3((unsigned)ivs::capped_blocks(total_queries, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    return check_launch("frame_rows_kernel");
-}
-
-namespace {
-__global__ __launch_bounds__(256) void i64_to_f64_kernel(const int64_t* a, double* o, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) o[i] = (double)a[i];
-}
-}  // namespace
-
-size_t ivs_frame_workspace_bytes(int64_t total_src, int64_t n_series, int32_t n_channels) {
-    if (total_src < 0 || n_series < 0 || n_channels < 0) return 0;
-    // the 1-D workspace, the positions as doubles, the channels' knot-rank tables
-    return ((ivs::interp1d_ws_bytes(total_src, n_series, n_channels) + 63) & ~(size_t)63) + (size_t)total_src * 8 +
-           (size_t)n_channels * (size_t)total_src * 4 + 64;
-}
-
-int ivs_frame_columns_f64(const ivs_frame_args* a, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "ivs_frame_columns_f64";
-    g_err[0] = 0;
-    if (!a) return fail(IVS_EINVAL, "%s: null args", fn);
-    if (!valid_method(a->method)) return fail(IVS_EINVAL, "%s: unknown method %d", fn, a->method);
-    if (a->n_series < 0 || a->total_src < 0 || a->total_queries < 0 || a->n_channels < 0 || a->n_valid < 0 || a->n_f < 0 ||
-        a->n_c < 0 || a->n_idx < 0)
-        return fail(IVS_EINVAL, "%s: negative size", fn);
-    if (a->n_series == 0 || a->total_queries == 0) return IVS_OK;
-    if (!a->src_pos || !a->src_off || !a->q_off) return fail(IVS_EINVAL, "%s: null offsets / positions", fn);
-    if (a->n_channels > 0 && (!a->yk || !a->chan_out || !a->status)) return fail(IVS_EINVAL, "%s: null channel arrays", fn);
-    if (a->n_channels > 0 && (a->yk_stride < a->total_src || a->chan_stride < a->total_queries))
-        return fail(IVS_EINVAL, "%s: channel stride smaller than row length", fn);
-    if (a->n_valid > 0 && (!a->valid || a->valid_stride < a->total_src)) return fail(IVS_EINVAL, "%s: null / short validity rows", fn);
-    if (a->n_f > 0 && (!a->fsrc || !a->f_rows || !a->f_out || a->f_stride < a->total_queries || a->fsrc_stride < a->total_src))
-        return fail(IVS_EINVAL, "%s: bad f64 column arguments", fn);
-    if (a->n_c > 0 && (!a->csrc || !a->c_rows || !a->c_out || a->c_stride < a->total_queries || a->csrc_stride < a->total_src))
-        return fail(IVS_EINVAL, "%s: bad code column arguments", fn);
-    if (a->n_idx > 0 && (!a->idx_rows || !a->idx_out || a->idx_stride < a->total_queries)) return fail(IVS_EINVAL, "%s: bad index row arguments", fn);
-    if (a->date_ns && (!a->keep || !a->first_ns)) return fail(IVS_EINVAL, "%s: date_ns needs keep and first_ns", fn);
-    if (a->sym_col >= a->n_c) return fail(IVS_EINVAL, "%s: sym_col outside the code columns", fn);
-    if (a->greeks) {
-        if (a->greeks_stride < a->total_queries) return fail(IVS_EINVAL, "%s: short greeks output", fn);
-        if (a->ch_iv < 0 || a->ch_iv >= a->n_channels || a->ch_underlying < 0 || a->ch_underlying >= a->n_channels || a->ch_ttm < 0 ||
-            a->ch_ttm >= a->n_channels || a->n_channels > 3)
-            return fail(IVS_EINVAL, "%s: Greeks need the three channels iv / underlying / ttm", fn);
-        if (a->g_strike >= a->n_valid || a->g_rate >= a->n_valid || a->g_put >= a->n_valid) return fail(IVS_EINVAL, "%s: Greek validity row outside valid", fn);
-        if ((a->g_strike >= 0 && !a->strike_src) || (a->g_rate >= 0 && !a->rate_src) || (a->g_put >= 0 && !a->put_src))
-            return fail(IVS_EINVAL, "%s: a present column needs its source array", fn);
-    }
-    if (a->total_src > 0x7fffffffLL || a->n_series * (int64_t)(a->n_channels > 0 ? a->n_channels : 1) > 0x7fffffffLL ||
-        (a->total_queries + ivs::FR_ROWS - 1) / ivs::FR_ROWS > 0x7fffffffLL)
-        return fail(IVS_ERANGE, "%s: batch too large for one launch", fn);
-    const size_t need = ivs_frame_workspace_bytes(a->total_src, a->n_series, a->n_channels);
-    if (!workspace || workspace_bytes < need) return fail(IVS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, workspace ? workspace_bytes : (size_t)0, need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ivs::Interp1dParams p{};
-    double* w = static_cast<double*>(workspace);
-    const size_t plane = (size_t)a->n_channels * (size_t)a->total_src;
-    p.wx = w; p.wy = w + plane; p.ws = w + 2 * plane; p.wcp = w + 3 * plane;
-    p.wn = reinterpret_cast<int32_t*>(w + 4 * plane);
-    double* xk = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(workspace) + ((ivs::interp1d_ws_bytes(a->total_src, a->n_series, a->n_channels) + 63) & ~(size_t)63));
-    p.wr = reinterpret_cast<int32_t*>(xk + a->total_src);
-    p.xk = xk; p.yk = a->yk; p.yk_stride = a->yk_stride; p.knot_off = a->src_off;
-    p.S = a->n_series; p.C = a->n_channels; p.total_knots = a->total_src;
-    p.xq = nullptr; p.q_off = a->q_off; p.total_q = a->total_queries;
-    p.out = a->chan_out; p.out_stride = a->chan_stride; p.status = a->status; p.method = a->method;
-    p.greeks = nullptr;
-    if (a->total_src > 0)
-        hipLaunchKernelGGL(i64_to_f64_kernel, dim3((unsigned)ivs::capped_blocks(a->total_src, num_cu())), dim3(256), 0, st, a->src_pos, xk, a->total_src);
-    if (a->n_channels > 0) {
-        hipLaunchKernelGGL(ivs::interp1d_prepare_kernel, dim3((unsigned)(a->n_series * a->n_channels)), dim3(256), 0, st, p);
-        const int rc = check_launch("interp1d_prepare_kernel");
-        if (rc) return rc;
-    }
-    ivs::FrameParams f{};
-    f.src_pos = a->src_pos; f.src_off = a->src_off; f.q_off = a->q_off; f.S = a->n_series; f.total_src = a->total_src; f.total_q = a->total_queries;
-    f.valid = a->valid; f.valid_stride = a->valid_stride; f.n_valid = a->n_valid;
-    f.fsrc = a->fsrc; f.fsrc_stride = a->fsrc_stride; f.f_rows = a->f_rows; f.n_f = a->n_f; f.f_out = a->f_out; f.f_stride = a->f_stride;
-    f.csrc = a->csrc; f.csrc_stride = a->csrc_stride; f.c_rows = a->c_rows; f.n_c = a->n_c; f.c_out = a->c_out; f.c_stride = a->c_stride;
-    f.idx_rows = a->idx_rows; f.n_idx = a->n_idx; f.idx_out = a->idx_out; f.idx_stride = a->idx_stride;
-    f.first_ns = a->first_ns; f.needs = a->needs; f.sym_col = a->sym_col; f.date_ns = a->date_ns; f.keep = a->keep;
-    f.g_strike = a->g_strike; f.g_rate = a->g_rate; f.g_put = a->g_put; f.strike_src = a->strike_src; f.rate_src = a->rate_src; f.put_src = a->put_src;
-    f.ch_iv = a->ch_iv; f.ch_S = a->ch_underlying; f.ch_T = a->ch_ttm; f.greeks = a->greeks; f.greeks_stride = a->greeks_stride;
-    const dim3 fgrid((unsigned)((a->total_queries + ivs::FR_ROWS - 1) / ivs::FR_ROWS));
-    ivs::with_method(ivs::frame_method_class(p.method), ivs::Methods<0, 1, 2>{}, [&](auto c) {
-        hipLaunchKernelGGL(ivs::frame_fused_kernel<decltype(c)::value>, fgrid, dim3(256), 0, st, f, p);
-    });
-    return check_launch("frame_fused_kernel");
-}
 
 int ivs_snapshot_assemble_f64(const ivs_snapshot_args* a, void*, size_t, void* stream) {
     const char* fn = "ivs_snapshot_assemble_f64";
@@ -987,82 +623,6 @@ int ivs_bs_implied_vol_f64(const double* price, const double* S, const double* K
     hipLaunchKernelGGL(ivs::bs_implied_vol_kernel, dim3((unsigned)ivs::capped_blocks(n, num_cu())), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     g_last_kernel = "bs_implied_vol_kernel";
     return check_launch("bs_implied_vol_kernel");
-}
-
-size_t ivs_surface_workspace_bytes(int64_t B, int32_t ragged) { return ivs::surface_ws_bytes(B, ragged != 0); }
-
-int ivs_surface_batch_f64(const double* K, const int64_t* k_off, int64_t k_stride, int32_t nK,
-                          const double* T, int64_t t_stride, int32_t nT,
-                          const double* sigma, int64_t B,
-                          const double* Kq, int64_t kq_stride, int32_t mK,
-                          const double* Tq, int64_t tq_stride, int32_t mT,
-                          double* out, int32_t* status, int32_t method, int32_t flags,
-                          void* workspace, size_t workspace_bytes, void* stream) {
-    g_err[0] = 0;
-    g_last_kernel = "";
-    if (!valid_method(method)) return fail(IVS_EINVAL, "ivs_surface_batch_f64: unknown method %d", method);
-    if (ivs::method_is_poly(method)) return fail(IVS_EINVAL, "ivs_surface_batch_f64: method %d ('barycentric' / 'krogh') is 1-D only", method);
-    if (B < 0 || nK < 0 || nT < 0 || mK < 0 || mT < 0) return fail(IVS_EINVAL, "ivs_surface_batch_f64: negative size");
-    if (B == 0 || mK == 0 || mT == 0) return IVS_OK;
-    if (!K || !T || !sigma || !Kq || !Tq || !out) return fail(IVS_EINVAL, "ivs_surface_batch_f64: null pointer");
-    if (nT < 1 || nT > ivs::GEN_NTMAX) return fail(IVS_ERANGE, "ivs_surface_batch_f64: nT=%d outside [1,%d]", nT, ivs::GEN_NTMAX);
-    if (nK < 1) return fail(IVS_ERANGE, "ivs_surface_batch_f64: nK=%d < 1", nK);
-    if (!k_off && k_stride != 0 && k_stride < nK) return fail(IVS_EINVAL, "ivs_surface_batch_f64: k_stride < nK");
-    if (t_stride < 0 || kq_stride < 0 || tq_stride < 0 || k_stride < 0)
-        return fail(IVS_EINVAL, "ivs_surface_batch_f64: negative stride");
-    if (ivs::generic_lds_bytes(nK, nT, ivs::method_is_cubic(method)) > 160 * 1024)
-        return fail(IVS_ERANGE, "ivs_surface_batch_f64: nK=%d x nT=%d needs %zu B of LDS (> 160 KiB)", nK, nT,
-                    ivs::generic_lds_bytes(nK, nT, ivs::method_is_cubic(method)));
-    const size_t need = ivs::surface_ws_bytes(B, k_off != nullptr);
-    if (!workspace || workspace_bytes < need)
-        return fail(IVS_ENOMEM, "ivs_surface_batch_f64: workspace %zu < %zu bytes (ivs_surface_workspace_bytes)",
-                    workspace ? workspace_bytes : (size_t)0, need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 255)
-        return fail(IVS_EINVAL, "ivs_surface_batch_f64: workspace must be 256-byte aligned");
-
-    ivs::SurfaceParams p;
-    p.K = K; p.k_off = k_off; p.k_stride = k_off ? 0 : k_stride; p.nK = nK; p.k_total = k_off ? k_stride : 0;
-    p.T = T; p.t_stride = t_stride; p.nT = nT;
-    p.sigma = sigma; p.B = B; p.map_groups = 1; p.tqs = nullptr; p.redo = nullptr; p.queue = nullptr; p.mode = nullptr;
-    p.Kq = Kq; p.kq_stride = kq_stride; p.mK = mK;
-    p.Tq = Tq; p.tq_stride = tq_stride; p.mT = mT;
-    p.out = out; p.status = status; p.method = method;
-    ivs::LaunchCtx cx;
-    current_device(cx.dev, cx.num_cu);
-    cx.st = static_cast<hipStream_t>(stream);
-    cx.ws = static_cast<unsigned char*>(workspace);
-    cx.ws_bytes = workspace_bytes;
-    cx.map_groups = (flags >> 8) & 0xff;
-
-    if (!(flags & IVS_FLAG_FORCE_GENERIC)) {
-        const int64_t need_blocks = (int64_t)cx.num_cu * 8;
-        cx.stamps = (g_stamp_buf && g_stamp_cap >= need_blocks * ivs::D_NSTAMP) ? g_stamp_buf : nullptr;
-        cx.grid_out = &g_last_grid;
-        // the fast paths in order; each answers 1 = dispatched, 0 = not covered (try the next), < 0 = launch error
-        const struct {
-            bool on;
-            int (*launch)(const ivs::SurfaceParams&, const ivs::LaunchCtx&, const char**);
-            const char* what;
-        } attempts[] = {{!cx.stamps && !(flags & IVS_FLAG_ONE_PASS), ivs::launch_surface_pass, "row-pass"},
-                        {true, ivs::launch_surface_dense, "dense"},
-                        {!g_stamp_buf, ivs::launch_surface_dense_var, "dense-var"}};
-        for (const auto& a : attempts) {
-            if (!a.on) continue;
-            const char* family = nullptr;
-            const int rc = a.launch(p, cx, &family);
-            if (rc == 1) {
-                set_last_kernel(family, method);
-                return check_launch(g_last_kernel);
-            }
-            if (rc < 0) return fail(IVS_ELAUNCH, "ivs_surface_batch_f64: %s dispatch failed", a.what);
-        }
-    }
-
-    if (!ivs::launch_surface_generic<false>(p, cx))
-        return fail(IVS_ERANGE, "ivs_surface_batch_f64: nK=%d x nT=%d needs %zu B of LDS (> 160 KiB)", nK, nT,
-                    ivs::generic_lds_bytes(nK, nT, ivs::method_is_cubic(method)));
-    g_last_kernel = "surface_generic_kernel";
-    return check_launch("surface_generic_kernel");
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 namespace ivs {
 
 constexpr int WAVE = 64;
+constexpr int ST_MAX_T = 64;       // rule T2: tenors per snapshot (one ballot); the host checks it for every call on SVI slices
 
 __device__ __forceinline__ double qnan() { return __builtin_nan(""); }
 

@@ -9,6 +9,8 @@
 
 namespace ivs {
 
+constexpr int IVS_MAX_DEV = 64;      // devices whose CU count and kernel attributes are cached per index
+
 // The methods a kernel family is instantiated for.  with_method calls f(std::integral_constant<int, M>{}) for the M of
 // the list that equals the run-time code and returns false (f not called) when the code is not in the list: the list is
 // what keeps unsupported (kernel, method) pairs from being instantiated.

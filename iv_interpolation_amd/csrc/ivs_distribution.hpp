@@ -13,7 +13,7 @@
 // took the row: every value is a function of the row's inputs and the grid index alone.
 #pragma once
 #include "ivs_device.hpp"
-#include "ivs_greeks.hpp"
+#include "ivs_bs_formulas.hpp"
 
 namespace ivs {
 

@@ -8,8 +8,8 @@
 //   coalesced store.  Queries default to the integer lattice 0..m-1 (the reference's RangeIndex).
 #pragma once
 #include "ivs_device.hpp"
-#include "ivs_greeks.hpp"
-#include "ivs_surface_dense.hpp"      // DPP helpers, scan_mat2
+#include "ivs_bs_formulas.hpp"
+#include "ivs_lanes.hpp"             // DPP helpers, scan_mat2, factor_tables
 
 namespace ivs {
 

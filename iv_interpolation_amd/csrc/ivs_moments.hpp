@@ -15,7 +15,7 @@
 // of each of the workgroup's snapshots.  Plain stores only, no atomics, no scratch.
 #pragma once
 #include "ivs_device.hpp"
-#include "ivs_greeks.hpp"
+#include "ivs_bs_formulas.hpp"
 
 namespace ivs {
 

@@ -15,12 +15,11 @@
 // the b128 reads of the rs-lanes and the b128 writes of the k-lanes bank-conflict free.
 // Surfaces that contain a NaN quote (or batches whose Tq is not ascending) are tagged with a
 // sentinel in out[b][0] and redone by the generic kernel in a second, filtered launch.
+// Device code only.  Launched from ivs_surface_dense.hip (surface_dense_kernel) and ivs_surface_tables_launch.hpp (tq_tables_kernel).
 #pragma once
-#include <atomic>
 #include <cstddef>
-#include <cstdlib>
 
-#include "ivs_dispatch.hpp"
+#include "ivs_lanes.hpp"
 #include "ivs_surface_generic.hpp"
 
 namespace ivs {
@@ -60,31 +59,6 @@ __host__ __device__ constexpr bool d_is_step(int m) { return m == IVS_NEAREST ||
 
 // codes of a query row in the maturity direction
 constexpr int TQ_LEFT = -1, TQ_HOLD = 15, TQ_NAN = 16;
-
-// ---- cross-lane helpers (DPP moves stay in the VALU; ds_bpermute shuffles cost an LDS round trip)
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ double dpp_f64(double old, double src) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, ROW_MASK, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, ROW_MASK, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-// old = 0.0 with full row / bank masks: bound_ctrl supplies the zero for lanes without a source, which saves the two
-// v_mov that would otherwise seed the destination with `old` before every pair of DPP moves
-template <int CTRL>
-__device__ __forceinline__ double dpp0_f64(double src) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-constexpr int DPP_ROW_SHL(int n) { return 0x100 | n; }   // lane i <- lane i+n (within a row of 16)
-constexpr int DPP_ROW_SHR(int n) { return 0x110 | n; }   // lane i <- lane i-n (within a row of 16)
-constexpr int DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138, DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
 
 // exponent of |x| inside [2^-500, 2^500]: the range where the division expansion applies no scaling
 __device__ __forceinline__ bool div_safe(double x) {
@@ -161,104 +135,6 @@ __device__ __forceinline__ void quad_weights(const XA& x, int n, int j, double x
     quad_basis(x, n, q + 2, xq, h0, h1, h2);
     const bool lowwin = q < jj;                          // window starts at jj - 1
     a0 = lowwin ? h0 : 0.0; a1 = lowwin ? h1 : h0; a2 = lowwin ? h2 : h1; a3 = lowwin ? 0.0 : h2;
-}
-
-// Inclusive scan over lanes 0..N-1 (N = 16 or 64) of 2x2 matrix products P_i <- P_i * P_{i-1} * ... * P_0.
-template <int N>
-__device__ __forceinline__ void scan_mat2(double& p00, double& p01, double& p10, double& p11, int lane) {
-    // lanes without a valid source (row start, rows masked off) receive the IDENTITY through the DPP
-    // `old` operand, so every lane multiplies unconditionally: no compare/select per step
-#define IVS_SCAN_STEP(CTRL, MASK)                                                              \
-    {                                                                                          \
-        const double e = dpp_f64<CTRL, MASK>(1.0, p00), h = dpp_f64<CTRL, MASK>(1.0, p11);     \
-        const double f = MASK == 0xF ? dpp0_f64<CTRL>(p01) : dpp_f64<CTRL, MASK>(0.0, p01);    \
-        const double g = MASK == 0xF ? dpp0_f64<CTRL>(p10) : dpp_f64<CTRL, MASK>(0.0, p10);    \
-        const double n00 = p00 * e + p01 * g, n01 = p00 * f + p01 * h;                         \
-        const double n10 = p10 * e + p11 * g, n11 = p10 * f + p11 * h;                         \
-        p00 = n00; p01 = n01; p10 = n10; p11 = n11;                                            \
-    }
-    (void)lane;
-    IVS_SCAN_STEP(DPP_ROW_SHR(1), 0xF)
-    IVS_SCAN_STEP(DPP_ROW_SHR(2), 0xF)
-    IVS_SCAN_STEP(DPP_ROW_SHR(4), 0xF)
-    IVS_SCAN_STEP(DPP_ROW_SHR(8), 0xF)
-    if (N > 16) {
-        IVS_SCAN_STEP(DPP_ROW_BCAST15, 0xA)     // rows 1,3 <- lane 15 of rows 0,2
-        IVS_SCAN_STEP(DPP_ROW_BCAST31, 0xC)     // rows 2,3 <- lane 31
-    }
-#undef IVS_SCAN_STEP
-}
-
-// Factorisation tables of the not-a-knot slope system on N knots X[0..N) (N = 64 or 16), computed by
-// lanes 0..N-1.  Conventions (oracle nak_slopes()):  forward  dp_i = PP_i*dyA + QQ_i*dyB - AL_i*dp_{i-1},
-// backward s_i = dp_i - CP_i*s_{i+1};  (dyA, dyB) = (dy_{i-1}, dy_i) for interior rows,
-// (dy_0, dy_1) for row 0 and (dy_{N-3}, dy_{N-2}) for row N-1.
-template <int N>
-__device__ __forceinline__ void factor_tables(const double* X, int lane, double& al, double& cp, double& pp,
-                                              double& qq, double& rdx_out) {
-    const int i = lane < N ? lane : N - 1;
-    const double x0 = X[i];
-    const double xp = X[i + 1 < N ? i + 1 : N - 1];
-    const double xpp = X[i + 2 < N ? i + 2 : N - 1];
-    const double xm = X[i > 0 ? i - 1 : 0];
-    const double xmm = X[i > 1 ? i - 2 : 0];
-    const double dxc = xp - x0;          // dx[i]
-    const double dxm = x0 - xm;          // dx[i-1]
-    const double dxp = xpp - xp;         // dx[i+1]
-    const double dxmm = xm - xmm;        // dx[i-2]
-    const double rdxc = refined_rcp(dxc);
-    double a, b, c;
-    if (i == 0) { a = 0.0; b = dxp; c = dxc + dxp; }
-    else if (i == N - 1) { a = dxmm + dxm; b = dxmm; c = 0.0; }
-    else { a = dxc; b = 2.0 * (dxm + dxc); c = dxm; }
-    const double rb = refined_rcp(b);
-    // g_i = a_i c_{i-1} / (b_i b_{i-1})
-    const double crb = c * rb;                                          // c_i / b_i
-    const double crb_prev = dpp0_f64<DPP_WAVE_SHR1>(crb);
-    const double g = i == 0 ? 0.0 : a * rb * crb_prev;
-    // omega_i = 1 - g_i / omega_{i-1}: prefix product of M_i = [[1,-g_i],[1,0]] (identity on lane 0)
-    double p00 = 1.0, p01 = i == 0 ? 0.0 : -g, p10 = i == 0 ? 0.0 : 1.0, p11 = i == 0 ? 1.0 : 0.0;
-    scan_mat2<N>(p00, p01, p10, p11, lane);
-    const double num = p00 + p01, den = p10 + p11;          // omega_i = num / den (applied to omega_0 = 1)
-    const double rw = i == 0 ? rb : den * rb * refined_rcp(num);   // 1 / w_i
-    al = a * rw;
-    cp = c * rw;
-    const double rdx_prev = dpp0_f64<DPP_WAVE_SHR1>(rdxc);   // 1/dx[i-1]
-    const double rdx_next = dpp0_f64<DPP_WAVE_SHL1>(rdxc);   // 1/dx[i+1]
-    // (DPP reads need the SOURCE lane active: keep every cross-lane move outside divergent branches)
-    const double rdxmm = dpp0_f64<DPP_WAVE_SHR1>(rdx_prev);  // 1/dx[i-2]
-    // edge rows need 1/d with d = x_{i+2}-x_i (row 0) or x_i - x_{i-2} (row N-1)
-    const double d = i == 0 ? dxc + dxp : dxmm + dxm;
-    const double rd = refined_rcp(d);
-    if (i == 0) {
-        pp = (dxc + 2.0 * d) * dxp * rdxc * rd * rw;         // * dy_0
-        qq = dxc * dxc * rdx_next * rd * rw;                 // * dy_1
-    } else if (i == N - 1) {
-        pp = dxm * dxm * rdxmm * rd * rw;                    // * dy_{N-3}
-        qq = (2.0 * d + dxm) * dxmm * rdx_prev * rd * rw;    // * dy_{N-2}
-    } else {
-        pp = 3.0 * dxc * rdx_prev * rw;                      // * dy_{i-1}
-        qq = 3.0 * dxm * rdxc * rw;                          // * dy_i
-    }
-    rdx_out = rdxc;
-}
-
-// segmented inclusive prefix / suffix products within aligned rows of 16 lanes
-__device__ __forceinline__ double seg16_prefix_prod(double v, int lane) {
-    (void)lane;                                   // out-of-row sources read as 1.0 (DPP `old`)
-    v *= dpp_f64<DPP_ROW_SHR(1)>(1.0, v);
-    v *= dpp_f64<DPP_ROW_SHR(2)>(1.0, v);
-    v *= dpp_f64<DPP_ROW_SHR(4)>(1.0, v);
-    v *= dpp_f64<DPP_ROW_SHR(8)>(1.0, v);
-    return v;
-}
-__device__ __forceinline__ double seg16_suffix_prod(double v, int lane) {
-    (void)lane;
-    v *= dpp_f64<DPP_ROW_SHL(1)>(1.0, v);
-    v *= dpp_f64<DPP_ROW_SHL(2)>(1.0, v);
-    v *= dpp_f64<DPP_ROW_SHL(4)>(1.0, v);
-    v *= dpp_f64<DPP_ROW_SHL(8)>(1.0, v);
-    return v;
 }
 
 // ---- local-slope methods (pchip, akima): a knot's slope depends on the 2 (pchip) or 4 (akima) neighbouring
@@ -547,10 +423,98 @@ static_assert(offsetof(TqShared, W) == DT * 4 * 8 && offsetof(TqShared, CP) == (
 typedef const double IVS_CONST* cdptr;
 __device__ __forceinline__ cdptr to_const(const double* p) { return (cdptr)p; }
 
+// Factor tables for n knots (run time) spread over NKB blocks of 64 lanes.  Tables are written at d_sl(i), i < n.
 template <int NKB>
 __device__ __forceinline__ void factor_tables_var(const double* X, int n, int lane, double* AL, double* CP, double* PP,
-                                                  double* QQ, double* PM, double* PI, double* PSI, double* RDX);
-__device__ __forceinline__ void local_tables_rt(const double* X, int n, int i, double& r0, double& r1, double& r2);
+                                                  double* QQ, double* PM, double* PI, double* PSI, double* RDX) {
+    double c00 = 1.0, c01 = 0.0, c10 = 0.0, c11 = 1.0;          // product of all matrices of the previous blocks
+    double carry_crb = 0.0, carry_rdx = 0.0, carry_rdx_prev = 0.0;
+#pragma unroll
+    for (int blk = 0; blk < NKB; ++blk) {
+        const int ir = blk * 64 + lane;
+        const bool in = ir < n;
+        const int i = in ? ir : n - 1;
+        const double x0 = X[i];
+        const double xp = X[i + 1 < n ? i + 1 : n - 1];
+        const double xpp = X[i + 2 < n ? i + 2 : n - 1];
+        const double xm = X[i > 0 ? i - 1 : 0];
+        const double xmm = X[i > 1 ? i - 2 : 0];
+        const double dxc = xp - x0, dxm = x0 - xm, dxp = xpp - xp, dxmm = xm - xmm;
+        const double rdxc = refined_rcp(dxc);
+        const bool first = ir == 0, last = ir == n - 1;
+        double a, b, c;
+        if (first) { a = 0.0; b = dxp; c = dxc + dxp; }
+        else if (last) { a = dxmm + dxm; b = dxmm; c = 0.0; }
+        else { a = dxc; b = 2.0 * (dxm + dxc); c = dxm; }
+        if (!in) { a = 0.0; b = 1.0; c = 0.0; }
+        const double rb = refined_rcp(b);
+        const double crb = c * rb;
+        double crb_prev = dpp0_f64<DPP_WAVE_SHR1>(crb);
+        if (blk > 0 && lane == 0) crb_prev = carry_crb;
+        const bool ident = first || !in;
+        const double g = ident ? 0.0 : a * rb * crb_prev;
+        double p00 = 1.0, p01 = ident ? 0.0 : -g, p10 = ident ? 0.0 : 1.0, p11 = ident ? 1.0 : 0.0;
+        scan_mat2<64>(p00, p01, p10, p11, lane);
+        if (blk > 0) {                                           // append the previous blocks' product on the right
+            const double n00 = p00 * c00 + p01 * c10, n01 = p00 * c01 + p01 * c11;
+            const double n10 = p10 * c00 + p11 * c10, n11 = p10 * c01 + p11 * c11;
+            p00 = n00; p01 = n01; p10 = n10; p11 = n11;
+        }
+        const double num = p00 + p01, den = p10 + p11;
+        const double rw = first ? rb : den * rb * refined_rcp(num);
+        const double al = a * rw, cp = c * rw;
+        double rdx_prev = dpp0_f64<DPP_WAVE_SHR1>(rdxc);
+        if (blk > 0 && lane == 0) rdx_prev = carry_rdx;
+        const double rdx_next = dpp0_f64<DPP_WAVE_SHL1>(rdxc);          // only row 0 uses it (never crosses a block)
+        double rdxmm = dpp0_f64<DPP_WAVE_SHR1>(rdx_prev);
+        if (blk > 0 && lane == 0) rdxmm = carry_rdx_prev;
+        const double d = first ? dxc + dxp : dxmm + dxm;
+        const double rd = refined_rcp(d);
+        double pm = 0.0, pp, qq;
+        if (first) {
+            pp = (dxc + 2.0 * d) * dxp * rdxc * rd * rw;         // * dy_0
+            qq = dxc * dxc * rdx_next * rd * rw;                 // * dy_1
+        } else if (last) {
+            pm = dxm * dxm * rdxmm * rd * rw;                    // * dy_{n-3}
+            pp = (2.0 * d + dxm) * dxmm * rdx_prev * rd * rw;    // * dy_{n-2}
+            qq = 0.0;
+        } else {
+            pp = 3.0 * dxc * rdx_prev * rw;                      // * dy_{i-1}
+            qq = 3.0 * dxm * rdxc * rw;                          // * dy_i
+        }
+        const double pi = seg16_prefix_prod(in ? -al : 1.0, lane);
+        const double psi = seg16_suffix_prod(in ? -cp : 1.0, lane);
+        {   // every slot is written: beyond n the NEUTRAL row (AL = -1, everything else 0) makes the forward sweep hold its
+            // value and the backward sweep harmless, so the sweeps need no per-step masks (the last system row has
+            // CP = 0, which cuts the backward recurrence off from whatever lies to its right)
+            const int kl = d_sl(ir);
+            AL[kl] = in ? al : -1.0; CP[kl] = in ? cp : 0.0; PP[kl] = in ? pp : 0.0; QQ[kl] = in ? qq : 0.0;
+            PM[kl] = in ? pm : 0.0; PI[kl] = pi; PSI[kl] = psi;
+            RDX[ir] = rdxc;
+        }
+        if (blk + 1 < NKB) {
+            c00 = readlane_f64(p00, 63); c01 = readlane_f64(p01, 63); c10 = readlane_f64(p10, 63); c11 = readlane_f64(p11, 63);
+            carry_crb = readlane_f64(crb, 63); carry_rdx = readlane_f64(rdxc, 63); carry_rdx_prev = readlane_f64(rdx_prev, 63);
+        }
+    }
+}
+
+// ---- local-slope methods (pchip, akima) with a run-time knot count (scheme: dense_strike_slopes_local)
+__device__ __forceinline__ void local_tables_rt(const double* X, int n, int i, double& r0, double& r1, double& r2) {
+    const bool in = i < n;
+    const int ii = in ? i : n - 1;
+    const double x0 = X[ii];
+    const double xp = X[ii + 1 < n ? ii + 1 : n - 1], xm = X[ii > 0 ? ii - 1 : 0];
+    const double dxc = xp - x0, dxm = x0 - xm;
+    const bool first = ii == 0, last = ii == n - 1;
+    const double h0 = first ? dxc : dxm;
+    const double h1 = first ? X[2] - X[1] : X[n - 2] - X[n - 3];
+    const double rs = refined_rcp(h0 + h1);
+    r0 = (in && !last) ? refined_rcp(dxc) : 0.0;
+    r1 = (first || last) ? (2.0 * h0 + h1) * rs : 2.0 * dxc + dxm;
+    r2 = (first || last) ? h0 * rs : dxc + 2.0 * dxm;
+    if (!in) { r1 = 0.0; r2 = 0.0; }
+}
 
 // T-phase: maturity-direction factor tables (LDS, TT) + per-query-row weights (registers, lane = tq; also W in LDS
 // when WLDS) + row counts per class.  Needs mT <= 64.  All 64 lanes must call it; ends with a barrier.
@@ -1022,14 +986,6 @@ __global__ __launch_bounds__(64) void tq_tables_kernel(SurfaceParams p, TqShared
     }
     if (lane < 24) o->queue[lane * QUEUE_STRIDE] = 0ull;
 }
-using TableMethods = Methods<IVS_LINEAR, IVS_CUBIC, IVS_CUBICSPLINE, IVS_SLINEAR, IVS_PCHIP, IVS_AKIMA, IVS_NEAREST, IVS_ZERO,
-                             IVS_FROM_DERIVATIVES, IVS_QUADRATIC>;
-template <bool NTR>
-inline void launch_tq_tables(const SurfaceParams& p, TqShared* o, hipStream_t st) {
-    with_method(p.method, TableMethods{}, [&](auto m) {
-        hipLaunchKernelGGL((tq_tables_kernel<decltype(m)::value, NTR>), dim3(1), dim3(64), 0, st, p, o);
-    });
-}
 // fills the uniform part of TqTables from the published tables (scalar loads)
 __device__ __forceinline__ void tq_from_shared(const void* tqs, TqTables& tt, const double*& TT, const double*& W) {
     const TqShared* g = static_cast<const TqShared*>(tqs);
@@ -1244,143 +1200,5 @@ __global__ __launch_bounds__(64, 2) void surface_dense_kernel(SurfaceParams p, u
         for (int i = 0; i < D_NSTAMP; ++i) dbg[(size_t)blockIdx.x * D_NSTAMP + i] = acc[i];
     }
 }
-
-// ---- host side -------------------------------------------------------------------------------------------------
-// Everything a launcher needs from the entry point: the CURRENT device (index, CU count), the caller's stream and
-// workspace, and the tuning override of the surface -> workgroup mapping (flags bits 8..15).  No process-global state:
-// the kernel attribute that unlocks > 64 KiB of dynamic LDS is per device and is tracked per device below.
-struct LaunchCtx {
-    int dev = 0, num_cu = 256;
-    hipStream_t st = nullptr;
-    unsigned char* ws = nullptr;
-    size_t ws_bytes = 0;
-    int map_groups = 0;
-    unsigned long long* stamps = nullptr;            // diagnostics (ivs_debug_stamps): buffer of the stamped dense kernel
-    int64_t* grid_out = nullptr;                     // diagnostics (ivs_debug_last_grid): receives the dense kernel's grid
-};
-constexpr int IVS_MAX_DEV = 64;
-constexpr size_t WS_TQ_BYTES = 8192;                 // TqShared at offset 0
-constexpr size_t WS_COUNTS_BYTES = 256;              // ragged: per-class counters
-constexpr int V_NCLASS = 4;                          // ragged: work lists (one per size class), B items each
-static_assert(sizeof(TqShared) <= WS_TQ_BYTES, "TqShared must fit its workspace slot");
-inline size_t surface_ws_bytes(int64_t B, bool ragged) {
-    return WS_TQ_BYTES + (ragged ? WS_COUNTS_BYTES + (size_t)V_NCLASS * (size_t)(B < 0 ? 0 : B) * 16 : 0);
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: set once per (kernel slot, device)
-inline void ensure_max_lds(const void* fn, int slot, int dev) {
-    static std::atomic<unsigned long long> done[IVS_MAX_DEV];
-    const int d = (dev >= 0 && dev < IVS_MAX_DEV) ? dev : 0;
-    const unsigned long long bit = 1ull << (slot & 63);
-    if (dev < 0 || dev >= IVS_MAX_DEV || !(done[d].load(std::memory_order_relaxed) & bit)) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done[d].fetch_or(bit, std::memory_order_relaxed);
-    }
-}
-
-// Launch the generic kernel (FILTER selects the "only tagged surfaces" variant).  Returns false if the
-// shape does not fit in LDS.
-template <bool FILTER>
-inline bool launch_surface_generic(const SurfaceParams& p, const LaunchCtx& cx) {
-    if (p.nK > 65535) return false;                               // 16-bit strike indices
-    const size_t lds = generic_lds_bytes(p.nK, p.nT, method_is_cubic(p.method));
-    if (lds > 160 * 1024) return false;
-    if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(surface_generic_kernel<FILTER>), FILTER ? 1 : 0, cx.dev);
-    int64_t grid = (int64_t)cx.num_cu * workgroups_per_cu(lds, 16) * 2;
-    const int64_t work = FILTER ? (p.B + 63) / 64 : p.B;
-    if (grid > work) grid = work;
-    hipLaunchKernelGGL(surface_generic_kernel<FILTER>, dim3((unsigned)grid), dim3(64), lds, cx.st, p);
-    return true;
-}
-
-// number of workgroup groups (= regions of the batch = work-queue heads; see the mapping comment in surface_dense_kernel);
-// `forced` > 0 is the caller's IVS_FLAG_MAP_GROUPS override (experiments).  With static striding small batches had to fall
-// back to one group (uneven shares); with the work queues they must NOT: one head for 3072 workgroups runs at the atomic
-// unit's pace (a 125 000-surface shard -- config 3 split over 8 GPUs -- ran at 252 instead of 317 M surfaces/s).
-inline int dense_map_groups(int64_t grid, int64_t B, int forced) {
-    int r = forced > 0 ? forced : 8;
-    if (r > 16) r = 16;                                   // queue heads in the workspace
-    while (r > 1 && (B < (int64_t)r * 256 || grid < r)) r >>= 1;      // tiny batches / grids: fewer, fuller regions
-    return r < 1 ? 1 : r;
-}
-
-// Maturity tables and queue heads of a call, shared by the surface launchers.  Shared T / Tq: the batch-wide tables go
-// into the workspace on the same stream (NTR: run-time maturity count; the table kernel also zeroes the queue heads);
-// per-surface maturities: no table kernel runs, the queue heads are zeroed here.  Returns false on a stream error.
-template <bool NTR>
-inline bool launch_tq_or_zero_queue(SurfaceParams& p, const LaunchCtx& cx, bool tsh, bool set_mode) {
-    TqShared* tq = reinterpret_cast<TqShared*>(cx.ws);
-    if (tsh) {
-        launch_tq_tables<NTR>(p, tq, cx.st);
-        p.tqs = tq;
-        p.redo = tq->redo;
-        p.mode = set_mode ? &tq->mode : nullptr;
-    } else {
-        if (hipMemsetAsync(tq->queue, 0, sizeof(TqShared::queue), cx.st) != hipSuccess) return false;
-        p.tqs = nullptr;
-        p.redo = nullptr;
-    }
-    p.queue = tq->queue;
-    return true;
-}
-
-// The tail of every fast-path launcher: surfaces the fast kernel tagged (missing quotes) go to the masked pass when the
-// batch is the fixed 64 x 16 form (shared T / Tq only, see launch_surface_masked), then the filtered generic kernel takes
-// whatever is still tagged (it returns at once when its counter is 0).
-inline bool launch_surface_masked(const SurfaceParams& p, const LaunchCtx& cx);      // ivs_surface_masked.hpp
-inline void launch_redo_tail(SurfaceParams& p, const LaunchCtx& cx, bool fixed64) {
-#ifndef IVS_DIAG_MINIMAL      // diagnostic builds (tools/pass_api.hip) skip the launchers that instantiate every kernel
-    if (fixed64 && launch_surface_masked(p, cx) && p.redo) ++p.redo;
-#endif
-    launch_surface_generic<true>(p, cx);
-}
-
-#ifndef IVS_DIAG_MINIMAL
-using DenseMethods = Methods<IVS_LINEAR, IVS_CUBIC, IVS_CUBICSPLINE, IVS_SLINEAR, IVS_PCHIP, IVS_AKIMA>;      // the one-pass kernels
-// Dense dispatch.  Returns 1 if dispatched (dense kernel + redo tail), 0 if the shape is not covered by a dense kernel,
-// -1 on a launch error.  *family: the kernel's name without its method.
-inline int launch_surface_dense(const SurfaceParams& p_in, const LaunchCtx& cx, const char** family) {
-    SurfaceParams p = p_in;
-    if (p.k_off || p.nK != DK || p.nT != DT) return 0;
-    if (p.k_stride != 0 && p.k_stride < DK) return 0;
-    if (reinterpret_cast<uintptr_t>(p.sigma) & 15) return 0;
-    if (p.mT > D_MAX_MT) return 0;
-    const size_t lds = dense_lds_bytes(p.mT);
-    if (generic_lds_bytes(p.nK, p.nT) > 160 * 1024) return 0;
-    int64_t grid = (int64_t)cx.num_cu * workgroups_per_cu(lds, 8);
-    if (grid > p.B) grid = p.B;
-    if (cx.grid_out) *cx.grid_out = grid;
-    p.map_groups = dense_map_groups(grid, p.B, cx.map_groups);
-    const bool tsh = p.t_stride == 0 && p.tq_stride == 0;
-    const bool wl = p.mT <= D_WLDS_MAX_MT;
-    if (!launch_tq_or_zero_queue<false>(p, cx, tsh, true)) return -1;
-    if (p.map_groups > 16) p.map_groups = 16;
-    if (cx.stamps) {   // diagnostic run: cubic and linear, shared T only
-        if (!tsh) return 0;
-        with_bool(p.method == IVS_CUBIC, [&](auto cubic) {
-            with_bool(wl, [&](auto w) {
-                hipLaunchKernelGGL((surface_dense_kernel<decltype(cubic)::value ? IVS_CUBIC : IVS_LINEAR, true, decltype(w)::value, true>), dim3((unsigned)grid), dim3(64),
-                                   lds, cx.st, p, cx.stamps);
-            });
-        });
-        *family = "surface_dense_kernel<stamp>";
-        return hipGetLastError() == hipSuccess ? 1 : -1;
-    }
-    const bool known = with_method(p.method, DenseMethods{}, [&](auto m) {
-        with_bool(tsh, [&](auto t) {
-            with_bool(wl, [&](auto w) {
-                hipLaunchKernelGGL((surface_dense_kernel<decltype(m)::value, decltype(t)::value, decltype(w)::value, false>), dim3((unsigned)grid), dim3(64), lds, cx.st, p,
-                                   nullptr);
-            });
-        });
-    });
-    if (!known) return 0;
-    *family = "surface_dense_kernel";
-    if (hipGetLastError() != hipSuccess) return -1;
-    launch_redo_tail(p, cx, true);
-    return 1;
-}
-
-#endif  // IVS_DIAG_MINIMAL
 
 }  // namespace ivs

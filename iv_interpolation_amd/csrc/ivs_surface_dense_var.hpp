@@ -27,82 +27,6 @@ __host__ __device__ inline size_t dense_var_lds_bytes(int mT) {
     return (size_t)(2 * DT * NKB * 72 + NKB * 64 + NKB * 64 + 64 + (mT <= D_WLDS_MAX_MT ? 4 * D_WLDS_MAX_MT : 0)) * 8;
 }
 
-// Factor tables for n knots (run time) spread over NKB blocks of 64 lanes.  Tables are written at d_sl(i), i < n.
-template <int NKB>
-__device__ __forceinline__ void factor_tables_var(const double* X, int n, int lane, double* AL, double* CP, double* PP,
-                                                  double* QQ, double* PM, double* PI, double* PSI, double* RDX) {
-    double c00 = 1.0, c01 = 0.0, c10 = 0.0, c11 = 1.0;          // product of all matrices of the previous blocks
-    double carry_crb = 0.0, carry_rdx = 0.0, carry_rdx_prev = 0.0;
-#pragma unroll
-    for (int blk = 0; blk < NKB; ++blk) {
-        const int ir = blk * 64 + lane;
-        const bool in = ir < n;
-        const int i = in ? ir : n - 1;
-        const double x0 = X[i];
-        const double xp = X[i + 1 < n ? i + 1 : n - 1];
-        const double xpp = X[i + 2 < n ? i + 2 : n - 1];
-        const double xm = X[i > 0 ? i - 1 : 0];
-        const double xmm = X[i > 1 ? i - 2 : 0];
-        const double dxc = xp - x0, dxm = x0 - xm, dxp = xpp - xp, dxmm = xm - xmm;
-        const double rdxc = refined_rcp(dxc);
-        const bool first = ir == 0, last = ir == n - 1;
-        double a, b, c;
-        if (first) { a = 0.0; b = dxp; c = dxc + dxp; }
-        else if (last) { a = dxmm + dxm; b = dxmm; c = 0.0; }
-        else { a = dxc; b = 2.0 * (dxm + dxc); c = dxm; }
-        if (!in) { a = 0.0; b = 1.0; c = 0.0; }
-        const double rb = refined_rcp(b);
-        const double crb = c * rb;
-        double crb_prev = dpp0_f64<DPP_WAVE_SHR1>(crb);
-        if (blk > 0 && lane == 0) crb_prev = carry_crb;
-        const bool ident = first || !in;
-        const double g = ident ? 0.0 : a * rb * crb_prev;
-        double p00 = 1.0, p01 = ident ? 0.0 : -g, p10 = ident ? 0.0 : 1.0, p11 = ident ? 1.0 : 0.0;
-        scan_mat2<64>(p00, p01, p10, p11, lane);
-        if (blk > 0) {                                           // append the previous blocks' product on the right
-            const double n00 = p00 * c00 + p01 * c10, n01 = p00 * c01 + p01 * c11;
-            const double n10 = p10 * c00 + p11 * c10, n11 = p10 * c01 + p11 * c11;
-            p00 = n00; p01 = n01; p10 = n10; p11 = n11;
-        }
-        const double num = p00 + p01, den = p10 + p11;
-        const double rw = first ? rb : den * rb * refined_rcp(num);
-        const double al = a * rw, cp = c * rw;
-        double rdx_prev = dpp0_f64<DPP_WAVE_SHR1>(rdxc);
-        if (blk > 0 && lane == 0) rdx_prev = carry_rdx;
-        const double rdx_next = dpp0_f64<DPP_WAVE_SHL1>(rdxc);          // only row 0 uses it (never crosses a block)
-        double rdxmm = dpp0_f64<DPP_WAVE_SHR1>(rdx_prev);
-        if (blk > 0 && lane == 0) rdxmm = carry_rdx_prev;
-        const double d = first ? dxc + dxp : dxmm + dxm;
-        const double rd = refined_rcp(d);
-        double pm = 0.0, pp, qq;
-        if (first) {
-            pp = (dxc + 2.0 * d) * dxp * rdxc * rd * rw;         // * dy_0
-            qq = dxc * dxc * rdx_next * rd * rw;                 // * dy_1
-        } else if (last) {
-            pm = dxm * dxm * rdxmm * rd * rw;                    // * dy_{n-3}
-            pp = (2.0 * d + dxm) * dxmm * rdx_prev * rd * rw;    // * dy_{n-2}
-            qq = 0.0;
-        } else {
-            pp = 3.0 * dxc * rdx_prev * rw;                      // * dy_{i-1}
-            qq = 3.0 * dxm * rdxc * rw;                          // * dy_i
-        }
-        const double pi = seg16_prefix_prod(in ? -al : 1.0, lane);
-        const double psi = seg16_suffix_prod(in ? -cp : 1.0, lane);
-        {   // every slot is written: beyond n the NEUTRAL row (AL = -1, everything else 0) makes the forward sweep hold its
-            // value and the backward sweep harmless, so the sweeps need no per-step masks (the last system row has
-            // CP = 0, which cuts the backward recurrence off from whatever lies to its right)
-            const int kl = d_sl(ir);
-            AL[kl] = in ? al : -1.0; CP[kl] = in ? cp : 0.0; PP[kl] = in ? pp : 0.0; QQ[kl] = in ? qq : 0.0;
-            PM[kl] = in ? pm : 0.0; PI[kl] = pi; PSI[kl] = psi;
-            RDX[ir] = rdxc;
-        }
-        if (blk + 1 < NKB) {
-            c00 = readlane_f64(p00, 63); c01 = readlane_f64(p01, 63); c10 = readlane_f64(p10, 63); c11 = readlane_f64(p11, 63);
-            carry_crb = readlane_f64(crb, 63); carry_rdx = readlane_f64(rdxc, 63); carry_rdx_prev = readlane_f64(rdx_prev, 63);
-        }
-    }
-}
-
 // Slopes of all 16 rows for run-time n.  Y/S planes have row stride RS = NKB*72; tables alias the S plane.
 template <int NKB>
 __device__ __forceinline__ void dense_strike_slopes_var(const double* Y, double* S, const double* Ksh, double* RDX, int n,
@@ -215,23 +139,6 @@ __device__ __forceinline__ void dense_strike_slopes_var(const double* Y, double*
     }
 }
 
-// ---- local-slope methods (pchip, akima) with a run-time knot count (scheme: dense_strike_slopes_local)
-__device__ __forceinline__ void local_tables_rt(const double* X, int n, int i, double& r0, double& r1, double& r2) {
-    const bool in = i < n;
-    const int ii = in ? i : n - 1;
-    const double x0 = X[ii];
-    const double xp = X[ii + 1 < n ? ii + 1 : n - 1], xm = X[ii > 0 ? ii - 1 : 0];
-    const double dxc = xp - x0, dxm = x0 - xm;
-    const bool first = ii == 0, last = ii == n - 1;
-    const double h0 = first ? dxc : dxm;
-    const double h1 = first ? X[2] - X[1] : X[n - 2] - X[n - 3];
-    const double rs = refined_rcp(h0 + h1);
-    r0 = (in && !last) ? refined_rcp(dxc) : 0.0;
-    r1 = (first || last) ? (2.0 * h0 + h1) * rs : 2.0 * dxc + dxm;
-    r2 = (first || last) ? h0 * rs : dxc + 2.0 * dxm;
-    if (!in) { r1 = 0.0; r2 = 0.0; }
-}
-
 // Final secant sequence F[i] = m_{kb-2+i}, i = 0..18, of one 16-knot segment of a row (yr: the row in the padded LDS
 // layout, kp = padded index of knot kb, R0 = 1/dx table, zero from interval n-1 on).  Akima: secants left of knot 0 and
 // beyond knot n-1 by linear extension of the secant sequence, F(i) = 2 F(i-1) - F(i-2).
@@ -341,64 +248,6 @@ __device__ __forceinline__ void dense_strike_slopes_local_var(const double* Y, d
 // the launch on config 5).  items == nullptr: the launch serves surfaces 0..B-1 of a uniform batch.
 struct VarItem { int32_t b; int32_t n; int64_t koff; };
 struct VarList { const VarItem* items; const int32_t* count; int qslot = 0; };      // qslot: work-queue head of this launch
-
-__global__ __launch_bounds__(256) void var_classify_kernel(SurfaceParams p, VarItem* l1, VarItem* l2, int32_t* counts) {
-    // 1024 consecutive surfaces per block and step, 4 per thread; block-level exclusive scan of the per-thread class
-    // counts, ONE global atomic per class, block and step (a per-wavefront atomic cost 0.36 ms per million surfaces)
-    __shared__ int wsum[2][4];
-    __shared__ int base_s[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int64_t b0 = (int64_t)blockIdx.x * 1024; b0 < p.B; b0 += (int64_t)gridDim.x * 1024) {      // block-uniform trip count
-        int64_t ko[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) { const int64_t b = b0 + 4 * tid + k; ko[k] = b <= p.B ? p.k_off[b] : 0; }
-        int cls[4]; int c[2] = {0, 0};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t b = b0 + 4 * tid + k;
-            const int64_t nn = ko[k + 1] - ko[k];
-            cls[k] = b >= p.B ? -1 : ((nn >= 4 && nn <= 64) ? 0 : ((nn >= 65 && nn <= 128) ? 1 : 2));
-            if (cls[k] >= 0 && (nn < 0 || nn > p.nK || ko[k] < 0 || (p.k_total > 0 && ko[k + 1] > p.k_total))) {
-                // offsets no kernel can serve (the LDS carve is sized by nK) or that leave the caller's K / sigma arrays
-                cls[k] = -1;
-                if (p.status) p.status[b] = IVS_ST_BAD_SHAPE;
-            }
-            if (cls[k] == 2) {                                  // not served by a dense kernel: generic redo pass
-                reinterpret_cast<unsigned long long*>(p.out + b * (int64_t)p.mT * p.mK)[0] = D_SENTINEL;
-                count_redo(p);
-            }
-            if (cls[k] == 0) ++c[0];
-            if (cls[k] == 1) ++c[1];
-        }
-        int pre[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            int incl = c[j];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d, 64); if (lane >= d) incl += o; }
-            if (lane == 63) wsum[j][wave] = incl;
-            pre[j] = incl - c[j];
-        }
-        __syncthreads();
-        if (tid < 2) {
-            const int tot = wsum[tid][0] + wsum[tid][1] + wsum[tid][2] + wsum[tid][3];
-            base_s[tid] = tot ? atomicAdd(&counts[tid], tot) : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            int w0 = 0;
-            for (int w = 0; w < wave; ++w) w0 += wsum[j][w];
-            pre[j] += base_s[j] + w0;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (cls[k] == 0) l1[pre[0]++] = VarItem{(int32_t)(b0 + 4 * tid + k), (int32_t)(ko[k + 1] - ko[k]), ko[k]};
-            if (cls[k] == 1) l2[pre[1]++] = VarItem{(int32_t)(b0 + 4 * tid + k), (int32_t)(ko[k + 1] - ko[k]), ko[k]};
-        }
-        __syncthreads();                                         // wsum / base_s are reused by the next step
-    }
-}
 
 // TSHARED: T and Tq shared by the batch (T-phase once per workgroup); otherwise per surface (t_stride / tq_stride),
 // the T-phase then runs inside the loop with its scratch in the S plane, which is free until the slopes are written.
@@ -587,26 +436,6 @@ __global__ __launch_bounds__(64, 2) void surface_dense_var_kernel(SurfaceParams 
         const int64_t it_next2 = wq.finish(pend, more);
         it = it_next; it_next = it_next2; b = b_next; n = n_next; koff = koff_next;
     }
-}
-
-// ---- host side shared by the launchers of the variable-shape kernels (one-pass and row-pass)
-// Work lists of a call.  Ragged batch: classified once into one list per size class (workspace: counters, then
-// V_NCLASS x B items); uniform batch: the empty lists.  need1 / need2: the size classes the call has to launch.
-struct VarWork { VarList wl1, wl2; bool need1, need2; };
-inline bool var_work_lists(const SurfaceParams& p, const LaunchCtx& cx, VarWork& w) {
-    VarItem* lists = nullptr;
-    int32_t* counts = nullptr;
-    if (p.k_off) {
-        counts = reinterpret_cast<int32_t*>(cx.ws + WS_TQ_BYTES);
-        lists = reinterpret_cast<VarItem*>(cx.ws + WS_TQ_BYTES + WS_COUNTS_BYTES);
-        if (hipMemsetAsync(counts, 0, WS_COUNTS_BYTES, cx.st) != hipSuccess) return false;
-        hipLaunchKernelGGL(var_classify_kernel, dim3((unsigned)capped_blocks(p.B, cx.num_cu, 1024, 8)), dim3(256), 0, cx.st, p, lists, lists + p.B, counts);
-    }
-    w.wl1 = VarList{lists, counts, 0};
-    w.wl2 = VarList{lists ? lists + p.B : nullptr, counts ? counts + 1 : nullptr, 1};
-    w.need1 = p.k_off ? true : p.nK <= 64;
-    w.need2 = p.nK > 64;
-    return true;
 }
 
 }  // namespace ivs

@@ -11,6 +11,7 @@
 //                       are exchanged through LDS and each wave writes half of the output rows;
 //             mK  > 64: the 64-query blocks alternate between the waves, no exchange.
 // Every barrier below is reached by both waves on every path (the redo decision is workgroup-uniform).
+// Device code only.  Launched, with the kernel of ivs_surface_dense_var.hpp, from ivs_surface_dense.hip.
 #pragma once
 #include <type_traits>
 
@@ -455,46 +456,5 @@ __global__ __launch_bounds__(128, 2) void surface_dense_var2_kernel(SurfaceParam
         it = it_next; b = b_next; n = n_next; koff = koff_next;
     }
 }
-
-#ifndef IVS_DIAG_MINIMAL
-// Dispatch for variable strike counts: class 4..64 on the one-wavefront kernel, class 65..128 on the two-wavefront
-// kernel, then the filtered generic redo pass.  Returns 1 if dispatched, 0 if the batch is not covered, -1 on a launch
-// error.  Scratch (ragged work lists + counters, batch-wide maturity tables) comes from the caller's workspace: no allocation.
-inline int launch_surface_dense_var(const SurfaceParams& p_in, const LaunchCtx& cx, const char** family) {
-    SurfaceParams p = p_in;
-    if (p.nT < 4 || p.nT > DT || p.mT > D_MAX_MT) return 0;
-    const bool tsh = p.t_stride == 0 && p.tq_stride == 0;
-    if (p.nK < 4 || p.nK > 128) return 0;
-    if (!p.k_off && p.k_stride != 0 && p.k_stride < p.nK) return 0;
-    if (generic_lds_bytes(p.nK, p.nT) > 160 * 1024) return 0;
-    if (!(d_is_hermite(p.method) || p.method == IVS_LINEAR || p.method == IVS_SLINEAR)) return 0;
-    const bool wl = p.mT <= D_WLDS_MAX_MT;
-    if (!launch_tq_or_zero_queue<true>(p, cx, tsh, false)) return -1;
-    if (p.k_off && p.B > 0x7fffffffLL) return 0;
-    VarWork vw;
-    if (!var_work_lists(p, cx, vw)) return -1;
-    auto grid_for = [&](size_t lds) {
-        const int64_t g = (int64_t)cx.num_cu * workgroups_per_cu(lds, 8);
-        return dim3((unsigned)(g > p.B ? p.B : g));
-    };
-    const bool known = with_method(p.method, DenseMethods{}, [&](auto m) {
-        constexpr int M = decltype(m)::value;
-        with_bool(wl, [&](auto w) {
-            with_bool(tsh, [&](auto t) {
-                constexpr bool W = decltype(w)::value, T = decltype(t)::value;
-                const size_t lds1 = dense_var_lds_bytes<1>(p.mT), lds2 = dense_var2_lds_bytes(p.mT);      // 40 KB: below the 64 KiB default limit
-                if (vw.need1) hipLaunchKernelGGL((surface_dense_var_kernel<M, 1, W, T>), grid_for(lds1), dim3(64), lds1, cx.st, p, vw.wl1);
-                if (vw.need2) hipLaunchKernelGGL((surface_dense_var2_kernel<M, W, T>), grid_for(lds2), dim3(128), lds2, cx.st, p, vw.wl2);
-            });
-        });
-    });
-    if (!known) return 0;
-    *family = "surface_dense_var_kernel";
-    if (hipGetLastError() != hipSuccess) return -1;
-    launch_redo_tail(p, cx, false);
-    return 1;
-}
-
-#endif  // IVS_DIAG_MINIMAL
 
 }  // namespace ivs

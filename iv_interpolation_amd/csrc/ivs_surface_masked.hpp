@@ -16,7 +16,8 @@
 // The methods with slopes or coefficients (cubic, cubicspline, quadratic, pchip, akima) ride on the same compaction in
 // ivs_surface_masked_pass.hpp, which borrows MK_RS, MK_MAXCOL, MaskedX and MaskedT from here.
 // Scope: uniform 64 x 16 batches, T / Tq shared, mK <= 64; runs in FILTER mode behind the dense / row-pass kernel (only
-// surfaces tagged with the sentinel).
+// surfaces tagged with the sentinel).  Device code only; launched, like the kernel of ivs_surface_masked_pass.hpp, from
+// ivs_surface_tail_launch.hpp.
 #pragma once
 #include "ivs_surface_dense.hpp"
 
@@ -191,28 +192,5 @@ __global__ __launch_bounds__(64, 3) void surface_masked_kernel(SurfaceParams p) 
       }
     }
 }
-
-}  // namespace ivs
-#include "ivs_surface_masked_pass.hpp"      // the row-pass form for the methods with slopes (needs the definitions above)
-namespace ivs {
-
-#ifndef IVS_DIAG_MINIMAL
-// Second pass behind the dense / row-pass kernel for uniform 64 x 16 batches: returns true when launched.
-using MaskedLerpMethods = Methods<IVS_LINEAR, IVS_SLINEAR, IVS_NEAREST, IVS_ZERO, IVS_FROM_DERIVATIVES>;      // surface_masked_kernel
-using MaskedSlopeMethods = Methods<IVS_CUBIC, IVS_CUBICSPLINE, IVS_QUADRATIC, IVS_PCHIP, IVS_AKIMA>;         // surface_masked_pass_kernel
-inline bool launch_surface_masked(const SurfaceParams& p, const LaunchCtx& cx) {
-    if (p.k_off || p.nK != DK || p.nT != DT || p.mK > 64 || p.mT > D_MAX_MT) return false;
-    if (p.t_stride != 0 || p.tq_stride != 0 || !p.tqs) return false;
-    int64_t grid = (int64_t)cx.num_cu * 12;
-    const int64_t work = (p.B + 63) / 64;
-    if (grid > work) grid = work;
-    return with_method(p.method, MaskedLerpMethods{}, [&](auto m) {
-               hipLaunchKernelGGL((surface_masked_kernel<decltype(m)::value>), dim3((unsigned)grid), dim3(64), masked_lds_bytes(), cx.st, p);
-           }) ||
-           with_method(p.method, MaskedSlopeMethods{}, [&](auto m) {
-               hipLaunchKernelGGL((surface_masked_pass_kernel<decltype(m)::value>), dim3((unsigned)grid), dim3(64), masked_pass_lds_bytes(), cx.st, p);
-           });
-}
-#endif
 
 }  // namespace ivs

@@ -22,11 +22,10 @@
 #pragma once
 #include "ivs_device.hpp"
 #include "ivs_distribution.hpp"
-#include "ivs_greeks.hpp"
+#include "ivs_bs_formulas.hpp"
 
 namespace ivs {
 
-constexpr int ST_MAX_T = 64;       // rule T2: tenors per snapshot (one ballot)
 constexpr int SC_WAVES = 4;        // wavefronts per workgroup of the calendar kernel
 constexpr int SC_MAX_GROUP = 32;   // rows per wavefront: two inversion lanes each
 constexpr int SC_STEPS = 52;       // rule C4

@@ -2,6 +2,7 @@
 // -DIVS_ABLATE=n to leave one phase out (see ivs_surface_dense.hpp).  ABI-2 entry points, no validation.  Never shipped.
 #include <hip/hip_runtime.h>
 #include "../iv_interpolation_amd/csrc/ivs_surface_dense.hpp"
+#include "../iv_interpolation_amd/csrc/ivs_surface_launch.hpp"
 extern "C" {
 int ivs_version(void) { return 2; }
 size_t ivs_surface_workspace_bytes(int64_t B, int32_t ragged) { return ivs::surface_ws_bytes(B, ragged != 0); }
@@ -17,7 +18,8 @@ int ivs_surface_batch_f64(const double* K, const int64_t* k_off, int64_t k_strid
     const int64_t grid = 2048;
     p.map_groups = ivs::dense_map_groups(grid, B, (flags >> 8) & 0xff);
     ivs::TqShared* tq = reinterpret_cast<ivs::TqShared*>(workspace);
-    ivs::launch_tq_tables<false>(p, tq, st);
+    if (method == IVS_CUBIC) hipLaunchKernelGGL((ivs::tq_tables_kernel<IVS_CUBIC, false>), dim3(1), dim3(64), 0, st, p, tq);
+    else hipLaunchKernelGGL((ivs::tq_tables_kernel<IVS_LINEAR, false>), dim3(1), dim3(64), 0, st, p, tq);
     p.tqs = tq; p.queue = tq->queue;
     const size_t lds = ivs::dense_lds_bytes(mT);
     if (method == IVS_CUBIC) hipLaunchKernelGGL((ivs::surface_dense_kernel<IVS_CUBIC, true, true, false>), dim3((unsigned)grid), dim3(64), lds, st, p, nullptr);

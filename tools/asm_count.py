@@ -1,8 +1,8 @@
-"""Static instruction counts of one kernel in an assembly listing (make -C iv_interpolation_amd/csrc asm -> build/ivs_api.s).
-    python tools/asm_count.py <mangled-name-substring> [listing ...]"""
-import re, sys
+"""Static instruction counts of one kernel in the assembly listings (make -C iv_interpolation_amd/csrc asm -> build/<unit>.s).
+    python tools/asm_count.py <mangled-name-substring> [listing ...]      (default: every build/*.s)"""
+import glob, re, sys
 pat = sys.argv[1]
-for path in sys.argv[2:] or ["build/ivs_api.s"]:
+for path in sys.argv[2:] or sorted(glob.glob("build/*.s")):
     t = open(path).read()
     for m in re.finditer(r"^(\S*%s\S*): +; @" % re.escape(pat), t, re.M):
         i = m.end(); j = t.index(".Lfunc_end", i)

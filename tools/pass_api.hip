@@ -1,7 +1,9 @@
 // Diagnostic library for tools/ab_bench.py: ONLY the row-pass kernel for uniform 64x16 batches (cubic).  Fast to build.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "../iv_interpolation_amd/csrc/ivs_surface_pass.hpp"
+#include "../iv_interpolation_amd/csrc/ivs_surface_pass_launch.hpp"
+#include "../iv_interpolation_amd/csrc/ivs_surface_tables_launch.hpp"
+#include "../iv_interpolation_amd/csrc/ivs_surface_tail_launch.hpp"
 #ifdef IVS_PASS_ENDSTAMP
 extern "C" int ivs_diag_ends(unsigned long long* host, int n_wg) {      // copies {start, end} of the last launch's workgroups
     static unsigned long long* buf = nullptr;
