@@ -39,6 +39,7 @@ RISK_TABLE = "iv_risk"
 EXPLAIN_TABLE = "iv_explain"
 VAR_TABLE = "iv_var"
 VAR_ATTRIB_TABLE = "iv_var_attrib"
+HEDGE_TABLE = "iv_hedge"
 SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
@@ -562,6 +563,67 @@ class CompleteOptimizedPipeline:
               + ", ".join(f"{t.get('symbol', t['strike'])} {t['mean_abs_share']:.1%}" for t in top.head(3).to_dict("records")))
         return {**result, "success": result["success"] and rows[0] > 0, "attrib_rows": rows[0], "top_contributors": top.to_dict("records")}
 
+    def run_hedge(self, book_file: Optional[str] = None, hedge_file: Optional[str] = None, rounds: int = 4, lag: int = 1, window: int = 256,
+                  levels=(0.05, 0.01), min_scenarios: int = 20) -> dict:
+        """Minimum-variance hedge: run_var, then per snapshot the instruments and sizes that remove the most of
+        the variance of the book's scenario P&L in at most `rounds` steps, and the VaR and ES of the hedged book, on the device.
+        The candidates are the CSV `hedge_file` (symbol; the word `underlying` names the underlying itself, every other symbol a
+        listed contract; at most 64 per underlying) or, without one, the underlying and up to 63 listed calls nearest the money
+        (snapshots.default_instruments).  One `iv_hedge` table per underlying (hedge_frame's columns) besides run_var's `iv_var`.  The
+        result has run_var's keys plus hedge_rows and median_left: the median share of the row's sum of squares left after the last
+        round over the snapshots with a hedge."""
+        from iv_interpolation_amd.engine import hedge_settings
+        from iv_interpolation_amd.snapshots import default_instruments, hedge_frame, listed_book
+        try:
+            hedge_settings(lag, window, levels, min_scenarios, 1, rounds, 0)
+        except (ValueError, TypeError) as e:
+            return {"success": False, "error": str(e)}
+        wanted = None
+        frames = self._interpolated_frames()
+        if not frames:
+            return {"success": False, "error": "No interpolated data found for the hedge"}
+        listed = listed_book(frames).set_index("symbol", drop=False)      # the candidates come from the chain, not from the book held
+        if hedge_file:
+            wanted = pd.read_csv(hedge_file)
+            if "symbol" not in wanted.columns:
+                return {"success": False, "error": f"{hedge_file}: no column 'symbol'"}
+            wanted = wanted["symbol"].astype(str).tolist()
+            unknown = [s for s in wanted if s.lower() != "underlying" and s not in listed.index]
+            if unknown:
+                return {"success": False, "error": f"{hedge_file}: not listed in the chain: {unknown[:4]}"}
+        rows, lefts, errors = [0], [], []
+
+        def hedge(builder, res, held, fit, reports):
+            if wanted is None:                               # the underlying and the 63 listed calls nearest the money
+                spots = np.asarray(_host_flags(res.spot), np.float64)
+                inst = default_instruments(listed[listed["underlying"] == res.underlying].reset_index(drop=True),
+                                           float(np.nanmedian(spots)) if np.isfinite(spots).any() else float("nan"))
+            else:                           # the underlying and this underlying's contracts, in the file's order
+                und = [s.lower() == "underlying" for s in wanted]
+                mine = [(s, u) for s, u in zip(wanted, und) if u or listed.loc[s, "underlying"] == res.underlying]
+                inst = pd.DataFrame({"symbol": [s for s, _ in mine], "strike": [np.nan if u else listed.loc[s, "strike"] for s, u in mine],
+                                     "expiry": [pd.NaT if u else listed.loc[s, "expiry"] for s, u in mine],
+                                     "callput": ["underlying" if u else listed.loc[s, "callput"] for s, u in mine]})
+                if not 1 <= len(inst) <= 64:
+                    errors.append(f"{hedge_file}: {len(inst)} instruments for {res.underlying}: 1 to 64 are supported")
+                    return
+            rep = builder.hedge([res], held, inst, reports, [fit], lag=lag, window=window, tail_probs=levels, min_scenarios=min_scenarios,
+                                rounds=rounds)
+            table = hedge_frame(rep, [res])
+            self.store.write_table(HEDGE_TABLE, res.underlying, table)
+            rows[0] += len(table)
+            if len(table):
+                lefts.extend(table.groupby("date", sort=False)["left"].last().tolist())
+            print(f"  {res.underlying}: {len(table)} hedge rows over {len(rep[0].labels)} instruments")
+        result = self._var_stage(book_file, lag, window, levels, min_scenarios, each=hedge)
+        if "error" in result:
+            return result
+        if errors:
+            return {"success": False, "error": errors[0]}
+        left = float(np.nanmedian(lefts)) if lefts else float("nan")
+        print(f"HEDGE COMPLETE: {rows[0]:,} rows; median share of the scenario variance left: {left:.3%}")
+        return {**result, "success": result["success"] and rows[0] > 0, "hedge_rows": rows[0], "median_left": left}
+
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
         quantiles, level probabilities and tails of every tenor row on the device, and one `iv_distribution` table per
@@ -742,12 +804,14 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "hedge", "all"], default="all")
     parser.add_argument("--book", metavar="FILE", help="--task risk / explain / var: a CSV of symbol, quantity (default: every listed contract, +1 each)")
     parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain / var: the pair is snapshot p and snapshot p + N (default 1)")
     parser.add_argument("--window", type=int, default=256, metavar="W", help="--task var: scenarios kept per snapshot (default 256)")
     parser.add_argument("--levels", default="0.05,0.01", metavar="P,P", help="--task var: tail probabilities (default 0.05,0.01)")
     parser.add_argument("--min-scenarios", type=int, default=20, metavar="N", help="--task var: fewer valid scenarios than N give no VaR (default 20)")
+    parser.add_argument("--hedge-with", metavar="FILE", help="--task hedge: a CSV of symbol (`underlying` or a listed contract), the candidates (default: the underlying and the 63 calls nearest the money)")
+    parser.add_argument("--rounds", type=int, default=4, metavar="K", help="--task hedge: at most K instruments per snapshot, 1..8 (default 4)")
     parser.add_argument("--group-by", choices=["expiry", "side"], default="expiry", help="--task varattrib: the groups the VaR is attributed to (default expiry)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
@@ -811,6 +875,9 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
             elif args.task == "varattrib":
                 result = pipeline.run_varattrib(args.book, args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()],
                                                 args.min_scenarios, args.group_by)
+            elif args.task == "hedge":
+                result = pipeline.run_hedge(args.book, args.hedge_with, args.rounds, args.lag, args.window,
+                                            [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios)
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

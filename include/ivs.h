@@ -909,6 +909,89 @@ typedef struct ivs_hsim_attrib_args {
 int ivs_svi_hsim_attrib_f64(const ivs_hsim_attrib_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Minimum-variance hedge of a book over its historical scenarios (rules M0-M11; additive to ABI 5): which of
+ * nH candidate instruments, in which sizes, remove the most of the variance of the book's scenario P&L row, in at most `rounds`
+ * steps of an orthogonal matching pursuit.  The book arrives as its row: pnl and scen_flags [B][window] as an ivs_svi_hsim_f64
+ * call on the same data wrote them (INPUTS here).  The candidates are inst_u, inst_tau [nH] (inst_stride 0) or [B][nH]
+ * (inst_stride nH), read as u and tau of ivs_svi_hsim_f64 under strike_mode, and inst_kind [nH] (uint8, device): 0 a call, 1 a put,
+ * 2 the underlying (its u and tau are not read); any other value is read as a call.
+ * Scenario s of snapshot p is ranked when it has no flag, its P&L is a number and it exists (s <= p - lag); n = the ranked
+ * scenarios, and the snapshot is active iff n >= min_scen and n > 0.  Every sum below runs over the ranked scenarios in ascending s,
+ * each product rounded, added serially from +0.0.
+ *   inst_pnl [B][window][nH]           stage 1: the P&L x of one unit of candidate h in scenario s: P' - P as ivs_svi_hsim_f64 forms the
+ *                                      term of an option at quantity 1.0 (the same bits), S' - S for the underlying; NaN when the
+ *                                      scenario is absent or void, the candidate is dead at p or has !(sigma' > 0).  +0.0 for a pair
+ *                                      whose ends carry the same bits.  Required; an INPUT of stage 2.
+ *   inst_value [B][nH]                 stage 1: the base price P, S for the underlying, NaN for a dead candidate.  May be NULL.
+ *   inst_flags [B][nH] (int32)         IVS_HG_DEAD: dead at p; IVS_HG_NEG_VOL: x is not a number in a ranked scenario; IVS_HG_FLAT:
+ *                                      !(g > 0) with g = sum x^2; IVS_HG_SPENT: its g fell to tol x g or below after the picks before
+ *                                      it (collinear with them), or its direction vanished.  A candidate with none of these is
+ *                                      usable.  IVS_HG_CHOSEN: picked in some round (informative).
+ *   pick [B][rounds] (int32)           the candidate of round k, -1 for an empty round.  Round k < n_forced takes candidate k when it
+ *                                      is eligible (usable, not chosen, g_k > tol x g) and is empty otherwise; a later round takes the
+ *                                      eligible candidate with the largest (a a) / g_k, a = sum x e on the current residual e, ties to
+ *                                      the lower h, and when nobody is eligible or !(gain > min_gain x E_k) it and every later round
+ *                                      are empty.
+ *   ss [B][rounds+1]                   E_0 = sum pnl^2 and the residual sum of squares E_k after every round.
+ *   n_rounds [B] (int32)               the rounds that are not empty.
+ *   hedge [B][nH]                      the quantity to ADD to the book per candidate, +0.0 for one not picked.
+ *   pnl_hedged [B][window]             pnl + sum over the picks in round order of hedge x inst_pnl, from pnl; NaN where not ranked.
+ *   var_h, es_h [B][nL], worst_h,      ivs_svi_hsim_f64's var, es, worst and n_valid on (pnl_hedged, scen_flags); with every round empty
+ *   n_scen [B] (int32)                 (an inactive snapshot included) they carry the bits of that call's own.
+ *   solo_qty, solo_left [B][nH]        the hedge with candidate h alone, 0.0 - a / g, and the share (E_0 - (a a) / g) / E_0 of the
+ *                                      variance it leaves; NaN for a candidate that is not usable.  Each may be NULL.
+ * On an inactive snapshot pick is -1, n_rounds 0, ss, hedge and the solo figures NaN; inst_pnl, inst_flags bits 0-2 and pnl_hedged
+ * (the row itself) stay as defined.  stages: 0 = everything, 1 = inst_pnl and inst_value alone, 2 = all but those, on inst_pnl as given.
+ * scen_per_wg: as in ivs_svi_hsim_f64, for stage 1.
+ *
+ * IVS_EINVAL and IVS_ERANGE as for ivs_svi_hsim_attrib_f64 (nH in the place of Q, without nG and the cap on a level's tail), plus
+ * IVS_ERANGE: nH > 64, rounds outside 1..8, n_forced outside 0..min(rounds, nH), tol not finite or outside [0, 1), min_gain not finite
+ * or negative, stages outside 0..2, B*window*nH >= 2^31.  B == 0, mT == 0 or nH == 0 is a no-op (nothing is written); the limits are
+ * checked before that.  A refused call launches nothing and touches no buffer.  No workspace, no allocation, no synchronisation
+ * (capturable); up to THREE launches.  When (rounds + 1) x window x 8 bytes exceed 48 KB, the first call of a process at that
+ * size (or a larger one than any before) also sets a function attribute of the selection kernel, which is no stream operation:
+ * make such a call once outside a capture before capturing it.
+ */
+enum {
+    IVS_HG_DEAD = 1,
+    IVS_HG_NEG_VOL = 2,
+    IVS_HG_FLAT = 4,
+    IVS_HG_SPENT = 8,
+    IVS_HG_CHOSEN = 16
+};
+typedef struct ivs_hedge_args {
+    const double* params; /* [B][mT][5] */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* inst_u; const double* inst_tau; int64_t inst_stride;
+    const uint8_t* inst_kind;  /* [nH] */
+    int32_t strike_mode;
+    int32_t mT; int32_t nH; /* 0..64 */ int64_t B;
+    int32_t lag;
+    int32_t window;            /* 1..1024 */
+    const double* tail_probs;  /* host */ int32_t nL; /* 0..8 */
+    int32_t min_scen;          /* >= 1 */
+    int32_t rounds;            /* 1..8 */
+    int32_t n_forced;          /* 0..min(rounds, nH) */
+    double tol; double min_gain;
+    int32_t stages;            /* 0 = all; 1 = inst_pnl only; 2 = selection and tail only */
+    int32_t scen_per_wg;       /* 0 = chosen by the call; 1..window = tuning / testing override, same bits */
+    const double* pnl;         /* [B][window], input */
+    const int32_t* scen_flags; /* [B][window], input */
+    double* inst_pnl;          /* [B][window][nH] */
+    int32_t* inst_flags;       /* [B][nH] */
+    int32_t* pick;             /* [B][rounds] */
+    double* ss;                /* [B][rounds+1] */
+    int32_t* n_rounds;         /* [B] */
+    double* hedge;             /* [B][nH] */
+    double* pnl_hedged;        /* [B][window] */
+    double* var_h; double* es_h; /* [B][nL] */
+    int32_t* worst_h; int32_t* n_scen; /* [B] */
+    double* solo_qty; double* solo_left; double* inst_value; /* [B][nH], each may be NULL */
+} ivs_hedge_args;
+int ivs_svi_hedge_f64(const ivs_hedge_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -997,7 +1080,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
  * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64,
- * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64 and ivs_svi_hsim_attrib_f64 set it too */
+ * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64, ivs_svi_hsim_attrib_f64 and ivs_svi_hedge_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

@@ -36,6 +36,10 @@ RK_MAX_SHOCKS, RK_MAX_GRID = 64, 1024
 HS_ABSENT, HS_VOID_PAIR, HS_NEG_VOL = 1, 2, 4
 HS_MAX_WINDOW, HS_MAX_LEVELS = 1024, 8
 HA_MAX_TAIL, HA_MAX_GROUPS = 64, 16
+# IVS_HG_*: per-candidate flags of the minimum-variance hedge; CHOSEN is informative, the others block a candidate
+HG_DEAD, HG_NEG_VOL, HG_FLAT, HG_SPENT, HG_CHOSEN = 1, 2, 4, 8, 16
+HG_MAX_INST, HG_MAX_ROUNDS = 64, 8
+HG_CALL, HG_PUT, HG_UNDERLYING = 0, 1, 2                         # inst_kind
 # IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
@@ -216,6 +220,18 @@ class HsimAttribArgs(C.Structure):
                 ("ces", _p), ("cvar", _p), ("ces_group", _p), ("cvar_group", _p), ("n_tail", _p), ("order", _p)]
 
 
+class HedgeArgs(C.Structure):
+    """ivs_hedge_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("inst_u", _p), ("inst_tau", _p), ("inst_stride", _i64), ("inst_kind", _p), ("strike_mode", _i32),
+                ("mT", _i32), ("nH", _i32), ("B", _i64), ("lag", _i32), ("window", _i32),
+                ("tail_probs", C.POINTER(C.c_double)), ("nL", _i32), ("min_scen", _i32), ("rounds", _i32), ("n_forced", _i32),
+                ("tol", C.c_double), ("min_gain", C.c_double), ("stages", _i32), ("scen_per_wg", _i32),
+                ("pnl", _p), ("scen_flags", _p), ("inst_pnl", _p), ("inst_flags", _p), ("pick", _p), ("ss", _p), ("n_rounds", _p),
+                ("hedge", _p), ("pnl_hedged", _p), ("var_h", _p), ("es_h", _p), ("worst_h", _p), ("n_scen", _p),
+                ("solo_qty", _p), ("solo_left", _p), ("inst_value", _p)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -267,6 +283,7 @@ SIGNATURES = {
     "ivs_svi_explain_f64": (C.c_int, [C.POINTER(ExplainArgs), _p, _sz, _p]),
     "ivs_svi_hsim_f64": (C.c_int, [C.POINTER(HsimArgs), _p, _sz, _p]),
     "ivs_svi_hsim_attrib_f64": (C.c_int, [C.POINTER(HsimAttribArgs), _p, _sz, _p]),
+    "ivs_svi_hedge_f64": (C.c_int, [C.POINTER(HedgeArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

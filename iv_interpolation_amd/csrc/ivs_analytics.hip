@@ -3,6 +3,7 @@
 // Argument validation happens here on the host; kernels assume validated shapes.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "ivs_arbitrage.hpp"
@@ -12,6 +13,7 @@
 #include "ivs_distribution.hpp"
 #include "ivs_explain.hpp"
 #include "ivs_greeks.hpp"
+#include "ivs_hedge.hpp"
 #include "ivs_host.hpp"
 #include "ivs_hsim.hpp"
 #include "ivs_hsim_attrib.hpp"
@@ -463,6 +465,87 @@ int ivs_svi_hsim_attrib_f64(const ivs_hsim_attrib_args* a, void*, size_t, void* 
     p.n_tail = a->n_tail; p.order = a->order;
     hipLaunchKernelGGL(ivs::svi_hsim_attrib_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
     return end_call("svi_hsim_attrib_kernel");
+}
+
+int ivs_svi_hedge_f64(const ivs_hedge_args* a, void*, size_t, void* stream) {
+    const char* fn = "ivs_svi_hedge_f64";
+    if (int rc = begin_call(fn, a)) return rc;
+    if (a->nL < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->nH, a->tq_stride, a->inst_stride, a->strike_mode)) return rc;
+    if (a->lag < 1) return fail(IVS_ERANGE, "%s: lag=%d < 1", fn, a->lag);
+    if (a->window < 1 || a->window > ivs::HS_MAX_WINDOW)
+        return fail(IVS_ERANGE, "%s: window=%d outside [1,%d]", fn, a->window, ivs::HS_MAX_WINDOW);
+    if (a->nL > ivs::HS_MAX_LEVELS) return fail(IVS_ERANGE, "%s: nL=%d > %d tail probabilities", fn, a->nL, ivs::HS_MAX_LEVELS);
+    if (a->nL > 0 && !a->tail_probs) return fail(IVS_EINVAL, "%s: null tail probabilities", fn);
+    for (int l = 0; l < a->nL; ++l)
+        if (!(a->tail_probs[l] > 0.0 && a->tail_probs[l] < 1.0))
+            return fail(IVS_ERANGE, "%s: tail probability %d (%g) is not inside (0, 1)", fn, l, a->tail_probs[l]);
+    if (a->min_scen < 1) return fail(IVS_ERANGE, "%s: min_scen=%d < 1", fn, a->min_scen);
+    if (a->scen_per_wg < 0 || a->scen_per_wg > a->window)
+        return fail(IVS_ERANGE, "%s: scen_per_wg=%d outside [0,%d]", fn, a->scen_per_wg, a->window);
+    if (a->nH > ivs::HG_MAX_INST) return fail(IVS_ERANGE, "%s: nH=%d > %d candidates", fn, a->nH, ivs::HG_MAX_INST);
+    if (a->rounds < 1 || a->rounds > ivs::HG_MAX_ROUNDS)
+        return fail(IVS_ERANGE, "%s: rounds=%d outside [1,%d]", fn, a->rounds, ivs::HG_MAX_ROUNDS);
+    if (a->n_forced < 0 || a->n_forced > a->rounds || a->n_forced > a->nH)
+        return fail(IVS_ERANGE, "%s: n_forced=%d outside [0,min(rounds=%d, nH=%d)]", fn, a->n_forced, a->rounds, a->nH);
+    if (!(a->tol >= 0.0 && a->tol < 1.0)) return fail(IVS_ERANGE, "%s: tol=%g is not inside [0, 1)", fn, a->tol);
+    if (!(a->min_gain >= 0.0 && a->min_gain < __builtin_inf())) return fail(IVS_ERANGE, "%s: min_gain=%g is not finite and >= 0", fn, a->min_gain);
+    if (a->stages < 0 || a->stages > 2) return fail(IVS_ERANGE, "%s: stages=%d outside [0,2]", fn, a->stages);
+    if (a->nH > 0 && a->B > 0x7fffffffLL / ((int64_t)a->window * a->nH))
+        return fail(IVS_ERANGE, "%s: %lld x %d x %d candidate scenarios exceed one launch", fn, (long long)a->B, a->window, a->nH);
+    if (a->B == 0 || a->mT == 0 || a->nH == 0) return IVS_OK;                                      // M11
+    if (!a->params || !a->Tq || !a->spot || !a->inst_u || !a->inst_tau || !a->inst_kind || !a->inst_pnl)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (a->stages != 1 && (!a->pnl || !a->scen_flags || !a->inst_flags || !a->pick || !a->ss || !a->n_rounds || !a->hedge || !a->pnl_hedged ||
+                           !a->worst_h || !a->n_scen || (a->nL > 0 && (!a->var_h || !a->es_h))))
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (int rc = check_query_launch(fn, "candidates", a->B, a->mT, a->nH, a->tq_stride, a->inst_stride)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (a->stages != 2) {
+        ivs::InstPnlParams p{};
+        p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.inst_u = a->inst_u; p.inst_tau = a->inst_tau; p.inst_kind = a->inst_kind;
+        p.tq_stride = a->tq_stride; p.inst_stride = a->inst_stride; p.rate = a->rate;
+        p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.window = a->window; p.nH = a->nH;
+        p.inst_pnl = a->inst_pnl; p.inst_value = a->inst_value;
+        // scenarios per workgroup: a workgroup is one wavefront, so thirty-two of them per CU before the runs are cut shorter (at
+        // lag 1 a long run stages and brackets every snapshot once, a short one its first end twice)
+        p.spw = items_per_wg(a->B, a->window, 32, a->window, a->scen_per_wg);
+        p.nchunk = (a->window + p.spw - 1) / p.spw;
+        const int64_t grid = a->B * p.nchunk;                   // <= B * window < 2^31
+        hipLaunchKernelGGL(ivs::svi_inst_pnl_kernel, dim3((unsigned)grid), dim3(64), 0, st, p);
+        if (int rc = end_call("svi_inst_pnl_kernel")) return rc;
+    }
+    if (a->stages != 1) {
+        ivs::PursuitParams p{};
+        p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.inst_u = a->inst_u; p.inst_tau = a->inst_tau; p.inst_kind = a->inst_kind;
+        p.tq_stride = a->tq_stride; p.inst_stride = a->inst_stride; p.rate = a->rate; p.tol = a->tol; p.min_gain = a->min_gain;
+        p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.window = a->window; p.nH = a->nH;
+        p.K = a->rounds; p.n_forced = a->n_forced; p.min_scen = a->min_scen;
+        p.pnl = a->pnl; p.scen_flags = a->scen_flags; p.inst_pnl = a->inst_pnl;
+        p.inst_flags = a->inst_flags; p.pick = a->pick; p.ss = a->ss; p.n_rounds = a->n_rounds;
+        p.hedge = a->hedge; p.pnl_hedged = a->pnl_hedged; p.solo_qty = a->solo_qty; p.solo_left = a->solo_left;
+        const size_t lds = (size_t)(a->rounds + 1) * a->window * sizeof(double);         // e and the directions: <= 72 KB
+        // above 48 KB the kernel's limit on dynamic LDS is raised first: a function attribute, not a stream operation, set once per
+        // size reached and remembered (so a call that repeats an earlier shape, a captured one included, makes no runtime call
+        // besides its launches); a size the device refuses is reported by the launch itself
+        static std::atomic<size_t> lds_allowed{48 * 1024};
+        if (lds > lds_allowed.load(std::memory_order_relaxed)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(ivs::hedge_pursuit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds) == hipSuccess)
+                lds_allowed.store(lds, std::memory_order_relaxed);
+            else
+                (void)hipGetLastError();
+        }
+        hipLaunchKernelGGL(ivs::hedge_pursuit_kernel, dim3((unsigned)a->B), dim3(64), lds, st, p);
+        if (int rc = end_call("hedge_pursuit_kernel")) return rc;
+        ivs::HsimTailParams t{};                                // H7 on the hedged row, the kernel as it is
+        t.pnl = a->pnl_hedged; t.scen_flags = a->scen_flags; t.window = a->window; t.nL = a->nL; t.min_scen = a->min_scen;
+        for (int l = 0; l < a->nL; ++l) t.tp[l] = a->tail_probs[l];
+        t.var = a->var_h; t.es = a->es_h; t.n_valid = a->n_scen; t.worst = a->worst_h;
+        hipLaunchKernelGGL(ivs::hsim_tail_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, st, t);
+        return end_call("hsim_tail_kernel");
+    }
+    return IVS_OK;
 }
 
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void*, size_t, void* stream) {

@@ -876,6 +876,95 @@ def svi_hsim_attrib(params, Tq, spot, rate, u, tau, qty, pnl, scen_flags, *, gro
     return out
 
 
+HEDGE_OUTPUTS = ("inst_pnl", "inst_flags", "pick", "ss", "n_rounds", "hedge", "pnl_hedged", "var_h", "es_h", "worst_h", "n_scen",
+                 "solo_qty", "solo_left", "inst_value")
+HEDGE_OPTIONAL = ("solo_qty", "solo_left", "inst_value")
+
+
+def hedge_settings(lag, window, tail_probs, min_scen, n_inst, rounds=4, n_forced=0, tol=1e-6, min_gain=1e-4, stages=0):
+    """The host-side checks of a minimum-variance hedge: those of hsim_settings, 1..64 candidates, 1..8
+    rounds, n_forced in 0..min(rounds, candidates), tol finite in [0, 1), min_gain finite and >= 0, stages 0, 1 or 2; ValueError
+    otherwise.  Returns (lag, window, tail_probs as a list, min_scen, rounds, n_forced, tol, min_gain, stages)."""
+    import math
+    lag, window, tp, min_scen, _ = hsim_settings(lag, window, tail_probs, min_scen)
+    if int(n_inst) != n_inst or not 1 <= n_inst <= _lib.HG_MAX_INST:
+        raise ValueError(f"{n_inst!r} candidate instruments: 1..{_lib.HG_MAX_INST} are supported")
+    if int(rounds) != rounds or not 1 <= rounds <= _lib.HG_MAX_ROUNDS:
+        raise ValueError(f"rounds {rounds!r} is not an integer in 1..{_lib.HG_MAX_ROUNDS}")
+    if int(n_forced) != n_forced or not 0 <= n_forced <= min(rounds, n_inst):
+        raise ValueError(f"n_forced {n_forced!r} is not an integer in 0..min(rounds, candidates) = {min(rounds, n_inst)}")
+    tol, min_gain = float(tol), float(min_gain)
+    if not (math.isfinite(tol) and 0.0 <= tol < 1.0):
+        raise ValueError(f"tol {tol!r} is not finite and inside [0, 1)")
+    if not (math.isfinite(min_gain) and min_gain >= 0.0):
+        raise ValueError(f"min_gain {min_gain!r} is not finite and >= 0")
+    if stages not in (0, 1, 2):
+        raise ValueError(f"stages {stages!r} is not 0, 1 or 2")
+    return lag, window, tp, min_scen, int(rounds), int(n_forced), tol, min_gain, int(stages)
+
+
+def svi_hedge(params, Tq, spot, rate, inst_u, inst_tau, inst_kind, pnl, scen_flags, *, lag: int = 1, window: int = 256,
+              tail_probs=DEFAULT_TAIL_PROBS, min_scen: int = 20, rounds: int = 4, n_forced: int = 0, tol: float = 1e-6,
+              min_gain: float = 1e-4, strike_mode: int = 0, want=HEDGE_OPTIONAL, out=None, stream=None, scen_per_wg: int = 0,
+              stages: int = 0):
+    """Minimum-variance hedge of a book over its historical scenarios (ivs_svi_hedge_f64; rules M0-M11 of DESIGN.md section 21):
+    which of the candidate instruments, in which sizes, remove the most of the variance of the book's scenario P&L row in at most
+    `rounds` steps of an orthogonal matching pursuit, and the VaR and ES of the hedged book.
+    params, Tq, spot, rate, strike_mode, lag, window, tail_probs, min_scen as in svi_hsim; pnl float64 and scen_flags int32
+    [B,window] as svi_hsim returned them for the book on the same inputs and settings.  inst_u, inst_tau float64 [nH] or [B,nH]: the
+    candidates, read as svi_hsim reads u and tau; inst_kind uint8 [nH]: _lib.HG_CALL, HG_PUT or HG_UNDERLYING (u and tau not read).
+    n_forced: the first n_forced rounds take candidates 0, 1, ... in turn ("hedge with exactly these"); the others pick greedily.
+    hedge_settings has the limits.
+    want: which of solo_qty, solo_left and inst_value [B,nH] to compute; one left out is neither computed nor written (None).
+    `out`: optional dict of preallocated outputs; with stages = 2 its inst_pnl [B,window,nH] is the input of the selection.
+    stages: 0 = everything, 1 = inst_pnl and inst_value alone, 2 = everything but those, from out's inst_pnl.
+    Snapshots without a slice (mT == 0) are refused with ValueError: the C call would be a no-op and nothing can be hedged.
+    Returns dict(inst_pnl [B,window,nH], inst_flags int32 [B,nH], pick int32 [B,rounds], ss [B,rounds+1], n_rounds int32 [B], hedge
+    [B,nH], pnl_hedged [B,window], var_h, es_h [B,nL], worst_h, n_scen int32 [B], solo_qty, solo_left, inst_value [B,nH]) of device
+    tensors; the flags are the _lib.HG_* bits."""
+    _check_strike_mode(strike_mode)
+    want = _wanted(want, HEDGE_OPTIONAL)
+    torch = require_device()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    if mT == 0:
+        raise ValueError("mT = 0: there is no slice to revalue a candidate on")
+    inst_u, inst_tau, inst_kind, _, nH = _option_queries(torch, B, inst_u, inst_tau, inst_kind)
+    if inst_kind is None:
+        raise TypeError("inst_kind must be a CUDA uint8 tensor [nH]")
+    lag, window, tp, min_scen, K, n_forced, tol, min_gain, stages = hedge_settings(lag, window, tail_probs, min_scen, nH, rounds, n_forced,
+                                                                                   tol, min_gain, stages)
+    hsim_settings(lag, window, tp, min_scen, scen_per_wg)
+    nL = len(tp)
+    pnl = _f64(torch, pnl, "pnl")
+    if not scen_flags.is_cuda or scen_flags.dtype != torch.int32:
+        raise TypeError("scen_flags must be a CUDA int32 tensor")
+    scen_flags = scen_flags.contiguous()
+    if tuple(pnl.shape) != (B, window) or tuple(scen_flags.shape) != (B, window):
+        raise ValueError(f"pnl and scen_flags must be [B, window] = {(B, window)}")
+    if stages == 2 and (out is None or out.get("inst_pnl") is None):
+        raise ValueError("stages = 2 selects on out['inst_pnl'] as given")
+    if B * window * nH >= 2 ** 31:
+        raise ValueError(f"{B} x {window} x {nH} candidate scenarios exceed one launch")
+    i32, f64 = torch.int32, torch.float64
+    one, two = stages != 2, stages != 1
+    shapes = {"inst_pnl": ((B, window, nH), f64, True), "inst_flags": ((B, nH), i32, two), "pick": ((B, K), i32, two),
+              "ss": ((B, K + 1), f64, two), "n_rounds": ((B,), i32, two), "hedge": ((B, nH), f64, two),
+              "pnl_hedged": ((B, window), f64, two), "var_h": ((B, nL), f64, two), "es_h": ((B, nL), f64, two),
+              "worst_h": ((B,), i32, two), "n_scen": ((B,), i32, two), "solo_qty": ((B, nH), f64, two and "solo_qty" in want),
+              "solo_left": ((B, nH), f64, two and "solo_left" in want), "inst_value": ((B, nH), f64, one and "inst_value" in want)}
+    out = _outputs(torch, out, shapes, params.device)
+    a = _slice_fields(_lib.HedgeArgs(), params, Tq, spot, rate)
+    a.inst_u, a.inst_tau, a.inst_stride, a.inst_kind = _ptr(inst_u), _ptr(inst_tau), (0 if inst_u.dim() == 1 else nH), _ptr(inst_kind)
+    a.strike_mode, a.nH, a.lag, a.window, a.tail_probs, a.nL, a.min_scen = int(strike_mode), nH, lag, window, _doubles(tp), nL, min_scen
+    a.rounds, a.n_forced, a.tol, a.min_gain, a.stages, a.scen_per_wg = K, n_forced, tol, min_gain, stages, int(scen_per_wg)
+    a.pnl, a.scen_flags = _ptr(pnl), _ptr(scen_flags)
+    for k in shapes:
+        setattr(a, k, _ptr(out[k]))
+    _call(torch, "ivs_svi_hedge_f64", a, stream, params, Tq, spot, inst_u, inst_tau, inst_kind, pnl, scen_flags, *out.values())
+
+    return {k: out[k] for k in shapes}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -33,7 +33,7 @@ from __future__ import annotations
 
 import re
 from dataclasses import dataclass
-from typing import List, Sequence, Union
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import pandas as pd
@@ -307,6 +307,42 @@ class VarAttributionReport:
     es: object                       # [B, nL]
 
 
+@dataclass
+class HedgeReport:
+    """One underlying's minimum-variance hedge of a book over its historical scenarios at every snapshot (rules M0-M11).  The value
+    arrays are device tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    lag: int
+    window: int
+    tail_probs: np.ndarray           # [nL]
+    min_scenarios: int
+    rounds: int
+    n_forced: int
+    tol: float
+    min_gain: float
+    labels: List[str]                # [nH] the candidates' names
+    strikes: np.ndarray              # [nH], NaN for the underlying
+    expiries: pd.DatetimeIndex       # [nH], NaT for the underlying
+    kind: np.ndarray                 # [nH] uint8: 0 call, 1 put, 2 the underlying
+    inst_pnl: object                 # [B, window, nH] the scenario P&L of one unit of every candidate
+    inst_flags: object               # [B, nH] int32, IVS_HG_*
+    pick: object                     # [B, rounds] int32: the candidate of every round, -1 = empty
+    ss: object                       # [B, rounds + 1] the sum of squares of the row before and after every round
+    n_rounds: object                 # [B] int32
+    hedge: object                    # [B, nH] the quantity to ADD to the book
+    pnl_hedged: object               # [B, window]
+    var_h: object                    # [B, nL] of the hedged book; losses are positive
+    es_h: object                     # [B, nL]
+    worst_h: object                  # [B] int32
+    n_scen: object                   # [B] int32
+    solo_qty: object                 # [B, nH] the hedge with that candidate alone
+    solo_left: object                # [B, nH] and the share of the variance it leaves
+    inst_value: object               # [B, nH] the candidates' prices
+    var: object                      # [B, nL] the VarReport's
+    es: object                       # [B, nL]
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -389,6 +425,13 @@ class HipBackend:
         return engine.svi_hsim_attrib(params, d(Tq), spot, rate, d(u), d(tau), d(qty), pnl, scen_flags, group=self._up(group, np.int32),
                                       n_groups=n_groups, lag=lag, window=window, tail_probs=tail_probs, min_scen=min_scen,
                                       is_put=self._up(is_put, np.uint8), strike_mode=strike_mode, stream=self.stream)
+
+    def hedge(self, params, Tq, spot, rate, inst_u, inst_tau, inst_kind, pnl, scen_flags, lag, window, tail_probs, min_scen, rounds,
+              n_forced, tol, min_gain, strike_mode):
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
+        return engine.svi_hedge(params, d(Tq), spot, rate, d(inst_u), d(inst_tau), self._up(inst_kind, np.uint8), pnl, scen_flags, lag=lag,
+                                window=window, tail_probs=tail_probs, min_scen=min_scen, rounds=rounds, n_forced=n_forced, tol=tol,
+                                min_gain=min_gain, strike_mode=strike_mode, stream=self.stream)
 
 
 def _host(a):
@@ -815,6 +858,57 @@ class SnapshotSurfaceBuilder:
             reports.append(VarAttributionReport(r.underlying, r.dates, lag, window, np.asarray(tp, np.float64), min_scenarios, strikes,
                                                 expiry, is_put, qty, group, labels, a["ces"], a["cvar"], a["ces_group"], a["cvar_group"],
                                                 a["n_tail"], a["order"], h.var, h.es))
+        return reports
+
+    # ------------------------------------------------------------------ hedge
+    def hedge(self, results: Sequence[SnapshotSurfaces], book: pd.DataFrame, instruments: Optional[pd.DataFrame] = None, var_reports=None,
+              svi_reports=None, rate: float = 0.0, lag: int = 1, window: int = 256, tail_probs=(0.05, 0.01), min_scenarios: int = 20,
+              rounds: int = 4, n_forced: int = 0, tol: float = 1e-6, min_gain: float = 1e-4, fit_rounds: int = 0) -> List["HedgeReport"]:
+        """The minimum-variance hedge of a book over the historical scenarios of var() (rules M0-M11): one HedgeReport per
+        underlying with, per snapshot, the instruments and sizes that remove the most of the variance of the book's scenario P&L in
+        at most `rounds` steps, the variance share left after every step and the VaR and ES of the hedged book.  instruments: a
+        frame with the columns symbol, strike, expiry and callput, at most 64 rows; a row whose callput is `underlying` is the
+        underlying itself (its strike and expiry are not read).  None: default_instruments(book, the underlying's median spot), drawn
+        from the book handed in (the builder sees no chain; complete_pipeline passes the listed contracts instead).
+        n_forced: the first n_forced rounds take instruments 0, 1, ... in turn ("hedge with exactly these").  var_reports: the
+        VarReports of var(results, book, ...) with the same rate and settings; None runs var() first.  fit_rounds: `rounds` of
+        svi() when the slices have to be fitted first.  svi_reports as for calendar()."""
+        from .engine import hedge_settings
+        if instruments is not None:
+            for c in ("symbol", "strike", "expiry", "callput"):
+                if c not in instruments.columns:
+                    raise KeyError(c)
+        svi_reports, _, _, _, _, own = self._book(
+            book, (results, svi_reports, rate, fit_rounds),
+            settings=lambda: hedge_settings(lag, window, tail_probs, min_scenarios, _HG_MAX_INST if instruments is None else len(instruments),
+                                            rounds, n_forced, tol, min_gain))
+        lag, window, tp, min_scenarios, rounds, _, tol, min_gain, _ = own
+        if var_reports is None:
+            var_reports = self.var(results, book, svi_reports, rate, lag, window, tp, min_scenarios)
+        if len(var_reports) != len(results):
+            raise ValueError(f"{len(var_reports)} VaR reports for {len(results)} surfaces")
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v, h in zip(results, svi_reports, var_reports):
+            if (h.lag, h.window, h.min_scenarios) != (lag, window, min_scenarios) or list(h.tail_probs) != list(tp):
+                raise ValueError("the VaR reports were made with other settings (lag, window, tail_probs, min_scenarios)")
+            inst = instruments if instruments is not None else default_instruments(book, float(np.nanmedian(_host(r.spot))) if len(r.dates) else np.nan)
+            if not 0 <= n_forced <= min(rounds, len(inst)):
+                raise ValueError(f"n_forced {n_forced!r} exceeds min(rounds, instruments) = {min(rounds, len(inst))}")
+            side = inst["callput"].astype(str).str.lower().str[:1]
+            if not side.isin(["c", "p", "u"]).all():
+                raise ValueError("an instrument's callput must start with c or p, or be `underlying`")
+            kind = np.where(side == "u", 2, np.where(side == "p", 1, 0)).astype(np.uint8)
+            strikes = np.where(kind == 2, np.nan, pd.to_numeric(inst["strike"], errors="coerce").to_numpy(np.float64))
+            expiry = pd.DatetimeIndex(pd.to_datetime(inst["expiry"]))
+            tau = self._tau(expiry, r.dates)
+            u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
+            g = be.hedge(v.params, r.tenors, r.spot, float(rate), u, tau, kind, h.pnl, h.scen_flags, lag, window, tp, min_scenarios, rounds,
+                         int(n_forced), tol, min_gain, 1)
+            reports.append(HedgeReport(r.underlying, r.dates, lag, window, np.asarray(tp, np.float64), min_scenarios, rounds, int(n_forced), tol,
+                                       min_gain, [str(x) for x in inst["symbol"]], strikes, expiry, kind, g["inst_pnl"], g["inst_flags"], g["pick"],
+                                       g["ss"], g["n_rounds"], g["hedge"], g["pnl_hedged"], g["var_h"], g["es_h"], g["worst_h"], g["n_scen"],
+                                       g["solo_qty"], g["solo_left"], g["inst_value"], h.var, h.es))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -1391,6 +1485,60 @@ def var_attribution_frame(reports: Sequence[VarAttributionReport], snapshots: Se
                              "ces": f64, "cvar": f64, "ces_share": f64, "n_tail": pd.Series(dtype=np.int32), "var_start": ns})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+_HG_MAX_INST = 64                    # IVS hedge: candidates per call
+
+
+def default_instruments(book: pd.DataFrame, spot: float, count: int = _HG_MAX_INST) -> pd.DataFrame:
+    """The default hedge instruments of SnapshotSurfaceBuilder.hedge: the underlying, then up to count - 1 CALLS of `book` (a
+    frame like listed_book's), sorted by (rank of |strike - spot| within their own expiry, expiry): the contract nearest the
+    money of every expiry first, the nearer expiries first, then the second nearest of every expiry, and so on.  Columns symbol,
+    strike, expiry, callput."""
+    side = book["callput"].astype(str).str.lower().str[:1]
+    calls = book[side == "c"].assign(strike=lambda d: pd.to_numeric(d["strike"], errors="coerce"), expiry=lambda d: pd.to_datetime(d["expiry"]))
+    calls = calls.dropna(subset=["strike", "expiry"])
+    if "symbol" not in calls.columns:
+        calls = calls.assign(symbol=[f"C-{k:g}-{e:%Y%m%d}" for k, e in zip(calls["strike"], calls["expiry"])])
+    dist = (calls["strike"] - spot).abs()
+    rank = dist.groupby(calls["expiry"]).rank(method="first")
+    calls = calls.assign(_rank=rank).sort_values(["_rank", "expiry"], kind="stable").head(max(count - 1, 0))
+    head = pd.DataFrame({"symbol": ["underlying"], "strike": [np.nan], "expiry": [pd.NaT], "callput": ["underlying"]})
+    body = pd.DataFrame({"symbol": calls["symbol"].astype(str).to_numpy(), "strike": calls["strike"].to_numpy(np.float64),
+                         "expiry": pd.DatetimeIndex(calls["expiry"]), "callput": "c"})
+    return pd.concat([head, body], ignore_index=True) if len(body) else head
+
+
+def hedge_frame(reports: Sequence[HedgeReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per snapshot with quotes > 0 and non-empty round, ordered by (underlying, date, round): columns underlying, date,
+    round, instrument (its label), quantity (to ADD to the book), left (the share E_{k+1} / E_0 of the row's sum of squares that
+    is left after the round) and, on the last non-empty round of the snapshot, var_<tp> / es_<tp> of the book and
+    var_<tp>_hedged / es_<tp>_hedged of the hedged book (NaN on the other rounds)."""
+    parts = []
+    levels = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        pick, ss, hedge = _host(p.pick)[keep].astype(np.int64), _host(p.ss)[keep], _host(p.hedge)[keep]
+        rows, ks = np.nonzero(pick >= 0)
+        c = pick[rows, ks]
+        last = np.zeros(len(rows), bool)
+        if len(rows):
+            last[np.flatnonzero(np.r_[rows[1:] != rows[:-1], True])] = True
+        with np.errstate(all="ignore"):
+            left = ss[rows, ks + 1] / ss[rows, 0]
+        cols = {"underlying": p.underlying, "date": p.dates[keep][rows], "round": ks.astype(np.int32),
+                "instrument": np.asarray(p.labels, object)[c] if len(c) else np.zeros(0, object), "quantity": hedge[rows, c], "left": left}
+        levels = [f"{float(tp):g}" for tp in p.tail_probs]
+        for n, tp in enumerate(levels):
+            for name, a in ((f"var_{tp}", p.var), (f"es_{tp}", p.es), (f"var_{tp}_hedged", p.var_h), (f"es_{tp}_hedged", p.es_h)):
+                cols[name] = np.where(last, _host(a)[keep][rows, n], np.nan)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "round": pd.Series(dtype=np.int32),
+                             "instrument": pd.Series(dtype=object), "quantity": f64, "left": f64})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date", "round"], kind="stable").reset_index(drop=True)
 
 
 def top_contributors(reports: Sequence[VarAttributionReport], snapshots: Sequence[SnapshotSurfaces], level: int = 0, count: int = 10) -> pd.DataFrame:
