@@ -40,6 +40,7 @@ EXPLAIN_TABLE = "iv_explain"
 VAR_TABLE = "iv_var"
 VAR_ATTRIB_TABLE = "iv_var_attrib"
 HEDGE_TABLE = "iv_hedge"
+WHATIF_TABLE = "iv_whatif"
 SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
@@ -573,40 +574,20 @@ class CompleteOptimizedPipeline:
         result has run_var's keys plus hedge_rows and median_left: the median share of the row's sum of squares left after the last
         round over the snapshots with a hedge."""
         from iv_interpolation_amd.engine import hedge_settings
-        from iv_interpolation_amd.snapshots import default_instruments, hedge_frame, listed_book
+        from iv_interpolation_amd.snapshots import hedge_frame
         try:
             hedge_settings(lag, window, levels, min_scenarios, 1, rounds, 0)
         except (ValueError, TypeError) as e:
             return {"success": False, "error": str(e)}
-        wanted = None
-        frames = self._interpolated_frames()
-        if not frames:
-            return {"success": False, "error": "No interpolated data found for the hedge"}
-        listed = listed_book(frames).set_index("symbol", drop=False)      # the candidates come from the chain, not from the book held
-        if hedge_file:
-            wanted = pd.read_csv(hedge_file)
-            if "symbol" not in wanted.columns:
-                return {"success": False, "error": f"{hedge_file}: no column 'symbol'"}
-            wanted = wanted["symbol"].astype(str).tolist()
-            unknown = [s for s in wanted if s.lower() != "underlying" and s not in listed.index]
-            if unknown:
-                return {"success": False, "error": f"{hedge_file}: not listed in the chain: {unknown[:4]}"}
+        candidates, error = self._candidates(hedge_file, "the hedge")
+        if error:
+            return {"success": False, "error": error}
         rows, lefts, errors = [0], [], []
 
         def hedge(builder, res, held, fit, reports):
-            if wanted is None:                               # the underlying and the 63 listed calls nearest the money
-                spots = np.asarray(_host_flags(res.spot), np.float64)
-                inst = default_instruments(listed[listed["underlying"] == res.underlying].reset_index(drop=True),
-                                           float(np.nanmedian(spots)) if np.isfinite(spots).any() else float("nan"))
-            else:                           # the underlying and this underlying's contracts, in the file's order
-                und = [s.lower() == "underlying" for s in wanted]
-                mine = [(s, u) for s, u in zip(wanted, und) if u or listed.loc[s, "underlying"] == res.underlying]
-                inst = pd.DataFrame({"symbol": [s for s, _ in mine], "strike": [np.nan if u else listed.loc[s, "strike"] for s, u in mine],
-                                     "expiry": [pd.NaT if u else listed.loc[s, "expiry"] for s, u in mine],
-                                     "callput": ["underlying" if u else listed.loc[s, "callput"] for s, u in mine]})
-                if not 1 <= len(inst) <= 64:
-                    errors.append(f"{hedge_file}: {len(inst)} instruments for {res.underlying}: 1 to 64 are supported")
-                    return
+            inst = candidates(res, errors)
+            if inst is None:
+                return
             rep = builder.hedge([res], held, inst, reports, [fit], lag=lag, window=window, tail_probs=levels, min_scenarios=min_scenarios,
                                 rounds=rounds)
             table = hedge_frame(rep, [res])
@@ -623,6 +604,92 @@ class CompleteOptimizedPipeline:
         left = float(np.nanmedian(lefts)) if lefts else float("nan")
         print(f"HEDGE COMPLETE: {rows[0]:,} rows; median share of the scenario variance left: {left:.3%}")
         return {**result, "success": result["success"] and rows[0] > 0, "hedge_rows": rows[0], "median_left": left}
+
+    def _candidates(self, file: Optional[str], what: str):
+        """The candidate instruments of run_hedge and run_whatif: (a function (res, errors) -> the frame of one underlying's
+        candidates, or None with a message appended to errors; an error message or None).  They are the CSV `file` (symbol; the word
+        `underlying` names the underlying itself, every other symbol a listed contract; at most 64 per underlying) or, without one,
+        the underlying and up to 63 listed calls nearest the money (snapshots.default_instruments)."""
+        from iv_interpolation_amd.snapshots import default_instruments, listed_book
+        wanted = None
+        frames = self._interpolated_frames()
+        if not frames:
+            return None, f"No interpolated data found for {what}"
+        listed = listed_book(frames).set_index("symbol", drop=False)      # the candidates come from the chain, not from the book held
+        if file:
+            wanted = pd.read_csv(file)
+            if "symbol" not in wanted.columns:
+                return None, f"{file}: no column 'symbol'"
+            wanted = wanted["symbol"].astype(str).tolist()
+            unknown = [s for s in wanted if s.lower() != "underlying" and s not in listed.index]
+            if unknown:
+                return None, f"{file}: not listed in the chain: {unknown[:4]}"
+
+        def candidates(res, errors):
+            if wanted is None:                               # the underlying and the 63 listed calls nearest the money
+                spots = np.asarray(_host_flags(res.spot), np.float64)
+                return default_instruments(listed[listed["underlying"] == res.underlying].reset_index(drop=True),
+                                           float(np.nanmedian(spots)) if np.isfinite(spots).any() else float("nan"))
+            und = [s.lower() == "underlying" for s in wanted]     # the underlying and this underlying's contracts, in the file's order
+            mine = [(s, u) for s, u in zip(wanted, und) if u or listed.loc[s, "underlying"] == res.underlying]
+            inst = pd.DataFrame({"symbol": [s for s, _ in mine], "strike": [np.nan if u else listed.loc[s, "strike"] for s, u in mine],
+                                 "expiry": [pd.NaT if u else listed.loc[s, "expiry"] for s, u in mine],
+                                 "callput": ["underlying" if u else listed.loc[s, "callput"] for s, u in mine]})
+            if not 1 <= len(inst) <= 64:
+                errors.append(f"{file}: {len(inst)} instruments for {res.underlying}: 1 to 64 are supported")
+                return None
+            return inst
+        return candidates, None
+
+    def run_whatif(self, book_file: Optional[str] = None, trades_file: Optional[str] = None, sizes=(0.25, 0.5, 0.75, 1.0, 1.25, 1.5, 2.0, 3.0),
+                   size_unit: str = "solo", top: int = 5, lag: int = 1, window: int = 256, levels=(0.05, 0.01), min_scenarios: int = 20) -> dict:
+        """What-if VaR and ES: run_var, then per snapshot what the VaR and the expected shortfall become when a
+        candidate trade is added to the book at every size of a ladder, on the device.  The candidates are the CSV `trades_file` or
+        the defaults, as for run_hedge; sizes: at most 16 rungs, multiples of every candidate's own minimum-variance size
+        (size_unit "solo") or quantities ("abs").  One `iv_whatif` table per underlying (whatif_frame's columns: the `top` trades per
+        snapshot by ES reduction at the first level) besides run_var's `iv_var`.  The result has run_var's keys plus whatif_rows and
+        median_es_reduction: the median over the snapshots of the best trade's ES reduction as a share of the book's ES."""
+        from iv_interpolation_amd.engine import whatif_settings
+        from iv_interpolation_amd.snapshots import whatif_frame
+        try:
+            sizes = [float(x) for x in sizes]
+            whatif_settings(lag, window, levels, min_scenarios, 1, len(sizes))
+            if size_unit not in ("solo", "abs"):
+                raise ValueError(f"size_unit {size_unit!r} is neither 'solo' nor 'abs'")
+            if int(top) != top or top < 1:
+                raise ValueError(f"top {top!r} is not an integer >= 1")
+        except (ValueError, TypeError) as e:
+            return {"success": False, "error": str(e)}
+        if not len(levels):
+            return {"success": False, "error": "the what-if ladder ranks trades by ES: at least one tail probability is needed"}
+        candidates, error = self._candidates(trades_file, "the what-if ladder")
+        if error:
+            return {"success": False, "error": error}
+        rows, gains, errors = [0], [], []
+
+        def whatif(builder, res, held, fit, reports):
+            inst = candidates(res, errors)
+            if inst is None:
+                return
+            rep = builder.whatif([res], held, inst, sizes, size_unit, reports, [fit], lag=lag, window=window, tail_probs=levels,
+                                 min_scenarios=min_scenarios)
+            table = whatif_frame(rep, [res], top=top)
+            self.store.write_table(WHATIF_TABLE, res.underlying, table)
+            rows[0] += len(table)
+            if len(table):
+                first = table.groupby("date", sort=False).first()
+                name = f"es_{float(levels[0]):g}"
+                with np.errstate(all="ignore"):
+                    gains.extend((-first[name + "_change"] / first[name].abs()).tolist())
+            print(f"  {res.underlying}: {len(table)} what-if rows over {len(rep[0].labels)} instruments x {len(sizes)} sizes")
+        result = self._var_stage(book_file, lag, window, levels, min_scenarios, each=whatif)
+        if "error" in result:
+            return result
+        if errors:
+            return {"success": False, "error": errors[0]}
+        gain = float(np.nanmedian(gains)) if gains else float("nan")
+        print(f"WHAT-IF COMPLETE: {rows[0]:,} rows; median ES reduction of the best trade: {gain:.3%}")
+        return {**result, "success": result["success"] and rows[0] > 0, "whatif_rows": rows[0], "median_es_reduction": gain}
 
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
@@ -804,7 +871,7 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "hedge", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "hedge", "whatif", "all"], default="all")
     parser.add_argument("--book", metavar="FILE", help="--task risk / explain / var: a CSV of symbol, quantity (default: every listed contract, +1 each)")
     parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain / var: the pair is snapshot p and snapshot p + N (default 1)")
     parser.add_argument("--window", type=int, default=256, metavar="W", help="--task var: scenarios kept per snapshot (default 256)")
@@ -812,6 +879,10 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
     parser.add_argument("--min-scenarios", type=int, default=20, metavar="N", help="--task var: fewer valid scenarios than N give no VaR (default 20)")
     parser.add_argument("--hedge-with", metavar="FILE", help="--task hedge: a CSV of symbol (`underlying` or a listed contract), the candidates (default: the underlying and the 63 calls nearest the money)")
     parser.add_argument("--rounds", type=int, default=4, metavar="K", help="--task hedge: at most K instruments per snapshot, 1..8 (default 4)")
+    parser.add_argument("--trades", metavar="FILE", help="--task whatif: a CSV of symbol (`underlying` or a listed contract), the candidate trades (default: as --hedge-with)")
+    parser.add_argument("--sizes", default="0.25,0.5,0.75,1,1.25,1.5,2,3", metavar="LIST", help="--task whatif: the ladder of sizes, at most 16 (default 0.25,...,3)")
+    parser.add_argument("--size-unit", choices=["solo", "abs"], default="solo", help="--task whatif: sizes are multiples of a candidate's own minimum-variance size, or quantities (default solo)")
+    parser.add_argument("--top", type=int, default=5, metavar="N", help="--task whatif: trades kept per snapshot (default 5)")
     parser.add_argument("--group-by", choices=["expiry", "side"], default="expiry", help="--task varattrib: the groups the VaR is attributed to (default expiry)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
@@ -878,6 +949,9 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
             elif args.task == "hedge":
                 result = pipeline.run_hedge(args.book, args.hedge_with, args.rounds, args.lag, args.window,
                                             [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios)
+            elif args.task == "whatif":
+                result = pipeline.run_whatif(args.book, args.trades, [float(x) for x in args.sizes.split(",") if x.strip()], args.size_unit, args.top,
+                                             args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios)
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

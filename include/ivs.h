@@ -992,6 +992,63 @@ typedef struct ivs_hedge_args {
 int ivs_svi_hedge_f64(const ivs_hedge_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * What-if VaR and expected shortfall of a book per candidate trade and size (rules W0-W9; additive to ABI 5):
+ * what the tail figures of ivs_svi_hsim_f64 become when q units of candidate h are ADDED to the book, for every snapshot p, every
+ * one of nH candidates and every one of nQ rungs of a ladder of sizes, in one launch.  The book arrives as its row (pnl, scen_flags
+ * [B][window], INPUTS), the candidates as for ivs_svi_hedge_f64 (inst_u, inst_tau, inst_stride, inst_kind), the ladder as size
+ * [nH][nQ] (size_stride 0) or [B][nH][nQ] (size_stride nH x nQ) on the device.  The ranked scenarios, n and "active" are those of
+ * ivs_svi_hedge_f64.
+ *   inst_pnl [B][window][nH]           stage 1: ivs_svi_hedge_f64's, by the same launch (the same bits).  Required; an INPUT of stage 2.
+ *   inst_value [B][nH]                 stage 1: as there.  May be NULL.
+ *   trade_flags [B][nH] (int32)        IVS_HG_NEG_VOL: x is not a number in a ranked scenario (a candidate dead at p is, whenever
+ *                                      n > 0).  No other bit is set.
+ *   var_w, es_w [B][nH][nQ][nL]        ivs_svi_hsim_f64's var and es of the row z_s = pnl_s + size x inst_pnl_s over the ranked
+ *                                      scenarios (the product rounded, then the sum): ascending, ties to the lower s, m = max(1,
+ *                                      floor(n x tp)), 0.0 - the m-th smallest and 0.0 - (the m smallest added serially from +0.0, / m).
+ *   worst_w [B][nH][nQ] (int32)        the scenario of rank 0 of that row.  May be NULL.
+ *                                      A rung is live iff its candidate has no flag, the snapshot is active, its size is finite and no
+ *                                      z of its row is NaN (inf - inf, 0 x inf); one that is not has NaN, NaN and -1.
+ *   best [B][nH][nL] (int32)           the live rung with the smallest es_w at that level (a NaN es_w never is), ties to the lower
+ *                                      rung; -1 without one.
+ *   var0, es0 [B][nL], worst0,         ivs_svi_hsim_f64's var, es, worst and n_valid of the row itself, formed here: the bits of that
+ *   n_scen [B] (int32)                 call's own on the same inputs.
+ * stages: 0 = everything, 1 = inst_pnl and inst_value alone, 2 = all but those, on inst_pnl as given.  scen_per_wg: for stage 1.
+ *
+ * IVS_EINVAL and IVS_ERANGE as for ivs_svi_hedge_f64 (without rounds, n_forced, tol and min_gain), plus IVS_ERANGE: nQ outside 1..16,
+ * B*nH*nQ*max(nL,1) >= 2^31; IVS_EINVAL: a size_stride that is neither 0 nor nH x nQ.  B == 0, mT == 0 or nH == 0 is a no-op (nothing
+ * is written); the limits are checked before that.  A refused call launches nothing and touches no buffer.  No workspace, no
+ * allocation, no synchronisation (capturable), no dynamic LDS; at most TWO launches.
+ */
+typedef struct ivs_whatif_args {
+    const double* params; /* [B][mT][5] */
+    const double* Tq; int64_t tq_stride;
+    const double* spot; double rate;
+    const double* inst_u; const double* inst_tau; int64_t inst_stride;
+    const uint8_t* inst_kind;  /* [nH] */
+    int32_t strike_mode;
+    int32_t mT; int32_t nH; /* 0..64 */ int64_t B;
+    int32_t lag;
+    int32_t window;            /* 1..1024 */
+    const double* tail_probs;  /* host */ int32_t nL; /* 0..8 */
+    int32_t min_scen;          /* >= 1 */
+    int32_t nQ;                /* 1..16 */
+    const double* size; int64_t size_stride; /* [nH][nQ] (0) or [B][nH][nQ] (nH * nQ), device */
+    int32_t stages;            /* 0 = all; 1 = inst_pnl only; 2 = the ladder only */
+    int32_t scen_per_wg;       /* 0 = chosen by the call; 1..window = tuning / testing override, same bits */
+    const double* pnl;         /* [B][window], input */
+    const int32_t* scen_flags; /* [B][window], input */
+    double* inst_pnl;          /* [B][window][nH] */
+    double* inst_value;        /* [B][nH], may be NULL */
+    int32_t* trade_flags;      /* [B][nH] */
+    double* var_w; double* es_w; /* [B][nH][nQ][nL] */
+    int32_t* worst_w;          /* [B][nH][nQ], may be NULL */
+    int32_t* best;             /* [B][nH][nL] */
+    double* var0; double* es0; /* [B][nL] */
+    int32_t* worst0; int32_t* n_scen; /* [B] */
+} ivs_whatif_args;
+int ivs_svi_whatif_f64(const ivs_whatif_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -1080,7 +1137,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
  * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64,
- * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64, ivs_svi_hsim_attrib_f64 and ivs_svi_hedge_f64 set it too */
+ * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64, ivs_svi_hsim_attrib_f64, ivs_svi_hedge_f64 and ivs_svi_whatif_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

@@ -40,6 +40,7 @@ HA_MAX_TAIL, HA_MAX_GROUPS = 64, 16
 HG_DEAD, HG_NEG_VOL, HG_FLAT, HG_SPENT, HG_CHOSEN = 1, 2, 4, 8, 16
 HG_MAX_INST, HG_MAX_ROUNDS = 64, 8
 HG_CALL, HG_PUT, HG_UNDERLYING = 0, 1, 2                         # inst_kind
+WI_MAX_RUNGS = 16                                                # sizes per candidate of the what-if ladder
 # IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
@@ -232,6 +233,17 @@ class HedgeArgs(C.Structure):
                 ("solo_qty", _p), ("solo_left", _p), ("inst_value", _p)]
 
 
+class WhatIfArgs(C.Structure):
+    """ivs_whatif_args of include/ivs.h (field for field)."""
+    _fields_ = [("params", _p), ("Tq", _p), ("tq_stride", _i64), ("spot", _p), ("rate", C.c_double),
+                ("inst_u", _p), ("inst_tau", _p), ("inst_stride", _i64), ("inst_kind", _p), ("strike_mode", _i32),
+                ("mT", _i32), ("nH", _i32), ("B", _i64), ("lag", _i32), ("window", _i32),
+                ("tail_probs", C.POINTER(C.c_double)), ("nL", _i32), ("min_scen", _i32), ("nQ", _i32),
+                ("size", _p), ("size_stride", _i64), ("stages", _i32), ("scen_per_wg", _i32),
+                ("pnl", _p), ("scen_flags", _p), ("inst_pnl", _p), ("inst_value", _p), ("trade_flags", _p),
+                ("var_w", _p), ("es_w", _p), ("worst_w", _p), ("best", _p), ("var0", _p), ("es0", _p), ("worst0", _p), ("n_scen", _p)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -284,6 +296,7 @@ SIGNATURES = {
     "ivs_svi_hsim_f64": (C.c_int, [C.POINTER(HsimArgs), _p, _sz, _p]),
     "ivs_svi_hsim_attrib_f64": (C.c_int, [C.POINTER(HsimAttribArgs), _p, _sz, _p]),
     "ivs_svi_hedge_f64": (C.c_int, [C.POINTER(HedgeArgs), _p, _sz, _p]),
+    "ivs_svi_whatif_f64": (C.c_int, [C.POINTER(WhatIfArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

@@ -25,6 +25,7 @@
 #include "ivs_ssvi.hpp"
 #include "ivs_svi.hpp"
 #include "ivs_svi_surface.hpp"
+#include "ivs_whatif.hpp"
 
 using namespace ivs::host;
 
@@ -39,6 +40,23 @@ void set_query_fields(P& p, const A* a) {
     p.mT = a->mT; p.strike_mode = a->strike_mode; p.Q = a->Q;
     if constexpr (!std::is_same_v<P, ivs::EvalParams>) p.is_put = a->is_put;
     if constexpr (!std::is_same_v<P, ivs::EvalParams> && !std::is_same_v<P, ivs::RiskParams>) p.qty = a->qty;
+}
+
+// stage 1 of the hedge and of the what-if ladder (M2, W2): svi_inst_pnl_kernel on the candidates of either args struct
+template <class A>
+int launch_inst_pnl(const A* a, hipStream_t st) {
+    ivs::InstPnlParams p{};
+    p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.inst_u = a->inst_u; p.inst_tau = a->inst_tau; p.inst_kind = a->inst_kind;
+    p.tq_stride = a->tq_stride; p.inst_stride = a->inst_stride; p.rate = a->rate;
+    p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.window = a->window; p.nH = a->nH;
+    p.inst_pnl = a->inst_pnl; p.inst_value = a->inst_value;
+    // scenarios per workgroup: a workgroup is one wavefront, so thirty-two of them per CU before the runs are cut shorter (at
+    // lag 1 a long run stages and brackets every snapshot once, a short one its first end twice)
+    p.spw = items_per_wg(a->B, a->window, 32, a->window, a->scen_per_wg);
+    p.nchunk = (a->window + p.spw - 1) / p.spw;
+    const int64_t grid = a->B * p.nchunk;                   // <= B * window < 2^31
+    hipLaunchKernelGGL(ivs::svi_inst_pnl_kernel, dim3((unsigned)grid), dim3(64), 0, st, p);
+    return end_call("svi_inst_pnl_kernel");
 }
 
 }  // namespace
@@ -501,20 +519,8 @@ int ivs_svi_hedge_f64(const ivs_hedge_args* a, void*, size_t, void* stream) {
         return fail(IVS_EINVAL, "%s: null pointer", fn);
     if (int rc = check_query_launch(fn, "candidates", a->B, a->mT, a->nH, a->tq_stride, a->inst_stride)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a->stages != 2) {
-        ivs::InstPnlParams p{};
-        p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.inst_u = a->inst_u; p.inst_tau = a->inst_tau; p.inst_kind = a->inst_kind;
-        p.tq_stride = a->tq_stride; p.inst_stride = a->inst_stride; p.rate = a->rate;
-        p.mT = a->mT; p.strike_mode = a->strike_mode; p.lag = a->lag; p.window = a->window; p.nH = a->nH;
-        p.inst_pnl = a->inst_pnl; p.inst_value = a->inst_value;
-        // scenarios per workgroup: a workgroup is one wavefront, so thirty-two of them per CU before the runs are cut shorter (at
-        // lag 1 a long run stages and brackets every snapshot once, a short one its first end twice)
-        p.spw = items_per_wg(a->B, a->window, 32, a->window, a->scen_per_wg);
-        p.nchunk = (a->window + p.spw - 1) / p.spw;
-        const int64_t grid = a->B * p.nchunk;                   // <= B * window < 2^31
-        hipLaunchKernelGGL(ivs::svi_inst_pnl_kernel, dim3((unsigned)grid), dim3(64), 0, st, p);
-        if (int rc = end_call("svi_inst_pnl_kernel")) return rc;
-    }
+    if (a->stages != 2)
+        if (int rc = launch_inst_pnl(a, st)) return rc;
     if (a->stages != 1) {
         ivs::PursuitParams p{};
         p.params = a->params; p.Tq = a->Tq; p.spot = a->spot; p.inst_u = a->inst_u; p.inst_tau = a->inst_tau; p.inst_kind = a->inst_kind;
@@ -544,6 +550,64 @@ int ivs_svi_hedge_f64(const ivs_hedge_args* a, void*, size_t, void* stream) {
         t.var = a->var_h; t.es = a->es_h; t.n_valid = a->n_scen; t.worst = a->worst_h;
         hipLaunchKernelGGL(ivs::hsim_tail_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, st, t);
         return end_call("hsim_tail_kernel");
+    }
+    return IVS_OK;
+}
+
+int ivs_svi_whatif_f64(const ivs_whatif_args* a, void*, size_t, void* stream) {
+    const char* fn = "ivs_svi_whatif_f64";
+    if (int rc = begin_call(fn, a)) return rc;
+    if (a->nL < 0 || a->size_stride < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (int rc = check_query_shape(fn, a->B, a->mT, a->nH, a->tq_stride, a->inst_stride, a->strike_mode)) return rc;
+    if (a->lag < 1) return fail(IVS_ERANGE, "%s: lag=%d < 1", fn, a->lag);
+    if (a->window < 1 || a->window > ivs::HS_MAX_WINDOW)
+        return fail(IVS_ERANGE, "%s: window=%d outside [1,%d]", fn, a->window, ivs::HS_MAX_WINDOW);
+    if (a->nL > ivs::HS_MAX_LEVELS) return fail(IVS_ERANGE, "%s: nL=%d > %d tail probabilities", fn, a->nL, ivs::HS_MAX_LEVELS);
+    if (a->nL > 0 && !a->tail_probs) return fail(IVS_EINVAL, "%s: null tail probabilities", fn);
+    for (int l = 0; l < a->nL; ++l)
+        if (!(a->tail_probs[l] > 0.0 && a->tail_probs[l] < 1.0))
+            return fail(IVS_ERANGE, "%s: tail probability %d (%g) is not inside (0, 1)", fn, l, a->tail_probs[l]);
+    if (a->min_scen < 1) return fail(IVS_ERANGE, "%s: min_scen=%d < 1", fn, a->min_scen);
+    if (a->scen_per_wg < 0 || a->scen_per_wg > a->window)
+        return fail(IVS_ERANGE, "%s: scen_per_wg=%d outside [0,%d]", fn, a->scen_per_wg, a->window);
+    if (a->nH > ivs::HG_MAX_INST) return fail(IVS_ERANGE, "%s: nH=%d > %d candidates", fn, a->nH, ivs::HG_MAX_INST);
+    if (a->nQ < 1 || a->nQ > ivs::WI_MAX_RUNGS) return fail(IVS_ERANGE, "%s: nQ=%d outside [1,%d]", fn, a->nQ, ivs::WI_MAX_RUNGS);
+    if (a->stages < 0 || a->stages > 2) return fail(IVS_ERANGE, "%s: stages=%d outside [0,2]", fn, a->stages);
+    if (a->nH > 0 && a->B > 0x7fffffffLL / ((int64_t)a->window * a->nH))
+        return fail(IVS_ERANGE, "%s: %lld x %d x %d candidate scenarios exceed one launch", fn, (long long)a->B, a->window, a->nH);
+    if (a->nH > 0 && a->B > 0x7fffffffLL / ((int64_t)a->nH * a->nQ * (a->nL > 0 ? a->nL : 1)))
+        return fail(IVS_ERANGE, "%s: %lld x %d x %d rungs at %d levels exceed one launch", fn, (long long)a->B, a->nH, a->nQ, a->nL);
+    if (a->size_stride != 0 && a->size_stride != (int64_t)a->nH * a->nQ)
+        return fail(IVS_EINVAL, "%s: size_stride=%lld is neither 0 nor nH*nQ", fn, (long long)a->size_stride);
+    if (a->B == 0 || a->mT == 0 || a->nH == 0) return IVS_OK;                                      // W9
+    if (!a->params || !a->Tq || !a->spot || !a->inst_u || !a->inst_tau || !a->inst_kind || !a->inst_pnl)
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (a->stages != 1 && (!a->pnl || !a->scen_flags || !a->size || !a->trade_flags || !a->worst0 || !a->n_scen ||
+                           (a->nL > 0 && (!a->var_w || !a->es_w || !a->best || !a->var0 || !a->es0))))
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    if (int rc = check_query_launch(fn, "candidates", a->B, a->mT, a->nH, a->tq_stride, a->inst_stride)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (a->stages != 2)
+        if (int rc = launch_inst_pnl(a, st)) return rc;                                            // W2
+    if (a->stages != 1) {
+        ivs::WhatIfParams p{};
+        p.pnl = a->pnl; p.scen_flags = a->scen_flags; p.inst_pnl = a->inst_pnl; p.size = a->size; p.size_stride = a->size_stride;
+        p.lag = a->lag; p.window = a->window; p.nH = a->nH; p.nQ = a->nQ; p.nL = a->nL; p.min_scen = a->min_scen;
+        for (int l = 0; l < a->nL; ++l) p.tp[l] = a->tail_probs[l];
+        p.trade_flags = a->trade_flags; p.var_w = a->var_w; p.es_w = a->es_w; p.worst_w = a->worst_w; p.best = a->best;
+        p.var0 = a->var0; p.es0 = a->es0; p.worst0 = a->worst0; p.n_scen = a->n_scen;
+        // candidates per workgroup: a wavefront takes one candidate at a time, so a workgroup takes four or more; all nH of a
+        // snapshot while the snapshots alone give every CU eight workgroups, fewer below that (W8: the same bits)
+        p.cpw = items_per_wg(a->B, (a->nH + ivs::WI_WAVES - 1) / ivs::WI_WAVES, 8, (a->nH + ivs::WI_WAVES - 1) / ivs::WI_WAVES, 0) * ivs::WI_WAVES;
+        p.nchunk = (a->nH + p.cpw - 1) / p.cpw;
+        const dim3 grid((unsigned)(a->B * p.nchunk)), block(ivs::WI_WAVES * 64);                   // <= B * nH < 2^31
+        const int nw = (a->window + 63) / 64;                   // registers per lane: the row of a window is 64 x NW scenarios
+        if (nw <= 1) hipLaunchKernelGGL(ivs::whatif_tail_kernel<1>, grid, block, 0, st, p);
+        else if (nw <= 2) hipLaunchKernelGGL(ivs::whatif_tail_kernel<2>, grid, block, 0, st, p);
+        else if (nw <= 4) hipLaunchKernelGGL(ivs::whatif_tail_kernel<4>, grid, block, 0, st, p);
+        else if (nw <= 8) hipLaunchKernelGGL(ivs::whatif_tail_kernel<8>, grid, block, 0, st, p);
+        else hipLaunchKernelGGL(ivs::whatif_tail_kernel<16>, grid, block, 0, st, p);
+        return end_call("whatif_tail_kernel");
     }
     return IVS_OK;
 }

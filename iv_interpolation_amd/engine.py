@@ -965,6 +965,88 @@ def svi_hedge(params, Tq, spot, rate, inst_u, inst_tau, inst_kind, pnl, scen_fla
     return {k: out[k] for k in shapes}
 
 
+WHATIF_OUTPUTS = ("inst_pnl", "inst_value", "trade_flags", "var_w", "es_w", "worst_w", "best", "var0", "es0", "worst0", "n_scen")
+WHATIF_OPTIONAL = ("worst_w", "inst_value")
+
+
+def whatif_settings(lag, window, tail_probs, min_scen, n_inst, n_rungs, stages=0):
+    """The host-side checks of a what-if ladder: those of hsim_settings, 1..64 candidates, 1..16 rungs,
+    stages 0, 1 or 2; ValueError otherwise.  Returns (lag, window, tail_probs as a list, min_scen, n_rungs, stages)."""
+    lag, window, tp, min_scen, _ = hsim_settings(lag, window, tail_probs, min_scen)
+    if int(n_inst) != n_inst or not 1 <= n_inst <= _lib.HG_MAX_INST:
+        raise ValueError(f"{n_inst!r} candidate instruments: 1..{_lib.HG_MAX_INST} are supported")
+    if int(n_rungs) != n_rungs or not 1 <= n_rungs <= _lib.WI_MAX_RUNGS:
+        raise ValueError(f"{n_rungs!r} sizes per candidate: 1..{_lib.WI_MAX_RUNGS} rungs are supported")
+    if stages not in (0, 1, 2):
+        raise ValueError(f"stages {stages!r} is not 0, 1 or 2")
+    return lag, window, tp, min_scen, int(n_rungs), int(stages)
+
+
+def svi_whatif(params, Tq, spot, rate, inst_u, inst_tau, inst_kind, pnl, scen_flags, size, *, inst_pnl=None, lag: int = 1,
+               window: int = 256, tail_probs=DEFAULT_TAIL_PROBS, min_scen: int = 20, strike_mode: int = 0, want=WHATIF_OPTIONAL,
+               out=None, stream=None, scen_per_wg: int = 0, stages: int = 0):
+    """What-if VaR and expected shortfall of a book per candidate trade and size (ivs_svi_whatif_f64; rules W0-W9 of DESIGN.md
+    section 22): what svi_hsim's var and es become when size[.., h, j] units of candidate h are added to the book, for every
+    snapshot, candidate and rung in one launch, and the rung with the smallest ES per candidate and level.
+    params, Tq, spot, rate, strike_mode, lag, window, tail_probs, min_scen, pnl, scen_flags, inst_u, inst_tau, inst_kind as in
+    svi_hedge.  size float64 [nH,nQ] (one ladder for all snapshots) or [B,nH,nQ]: the quantity of candidate h to ADD at rung j; a
+    rung whose size is not finite is not live.  whatif_settings has the limits.
+    inst_pnl: with stages = 2 the rows [B,window,nH] the ladder is formed on (out['inst_pnl'] serves as well).
+    want: which of worst_w [B,nH,nQ] and inst_value [B,nH] to compute; one left out is neither computed nor written (None).
+    `out`: optional dict of preallocated outputs.  stages: 0 = everything, 1 = inst_pnl and inst_value alone, 2 = everything but those.
+    Snapshots without a slice (mT == 0) are refused with ValueError, as svi_hedge refuses them.
+    Returns dict(inst_pnl [B,window,nH], inst_value [B,nH], trade_flags int32 [B,nH], var_w, es_w [B,nH,nQ,nL], worst_w int32
+    [B,nH,nQ], best int32 [B,nH,nL], var0, es0 [B,nL], worst0, n_scen int32 [B]) of device tensors; a rung that is not live has
+    NaN, NaN and -1."""
+    _check_strike_mode(strike_mode)
+    want = _wanted(want, WHATIF_OPTIONAL)
+    torch = require_device()
+    params, Tq, spot, B, mT = _svi_inputs(torch, params, Tq, spot)
+    if mT == 0:
+        raise ValueError("mT = 0: there is no slice to revalue a candidate on")
+    inst_u, inst_tau, inst_kind, _, nH = _option_queries(torch, B, inst_u, inst_tau, inst_kind)
+    if inst_kind is None:
+        raise TypeError("inst_kind must be a CUDA uint8 tensor [nH]")
+    size = _f64(torch, size, "size")
+    if size.dim() not in (2, 3) or size.shape[-2] != nH or (size.dim() == 3 and size.shape[0] != B):
+        raise ValueError(f"size must be [nH, nQ] or [B, nH, nQ] with nH = {nH}")
+    nQ = size.shape[-1]
+    lag, window, tp, min_scen, nQ, stages = whatif_settings(lag, window, tail_probs, min_scen, nH, nQ, stages)
+    hsim_settings(lag, window, tp, min_scen, scen_per_wg)
+    nL = len(tp)
+    pnl = _f64(torch, pnl, "pnl")
+    if not scen_flags.is_cuda or scen_flags.dtype != torch.int32:
+        raise TypeError("scen_flags must be a CUDA int32 tensor")
+    scen_flags = scen_flags.contiguous()
+    if tuple(pnl.shape) != (B, window) or tuple(scen_flags.shape) != (B, window):
+        raise ValueError(f"pnl and scen_flags must be [B, window] = {(B, window)}")
+    out = dict(out or {})
+    if inst_pnl is not None:
+        if out.get("inst_pnl") is not None and out["inst_pnl"] is not inst_pnl:
+            raise ValueError("inst_pnl and out['inst_pnl'] are two tensors: give one")
+        out["inst_pnl"] = inst_pnl
+    if stages == 2 and out.get("inst_pnl") is None:
+        raise ValueError("stages = 2 forms the ladder on inst_pnl as given")
+    if B * window * nH >= 2 ** 31 or B * nH * nQ * max(nL, 1) >= 2 ** 31:
+        raise ValueError(f"{B} snapshots x {nH} candidates x {window} scenarios or x {nQ} rungs x {nL} levels exceed one launch")
+    i32, f64 = torch.int32, torch.float64
+    one, two = stages != 2, stages != 1
+    shapes = {"inst_pnl": ((B, window, nH), f64, True), "inst_value": ((B, nH), f64, one and "inst_value" in want),
+              "trade_flags": ((B, nH), i32, two), "var_w": ((B, nH, nQ, nL), f64, two), "es_w": ((B, nH, nQ, nL), f64, two),
+              "worst_w": ((B, nH, nQ), i32, two and "worst_w" in want), "best": ((B, nH, nL), i32, two),
+              "var0": ((B, nL), f64, two), "es0": ((B, nL), f64, two), "worst0": ((B,), i32, two), "n_scen": ((B,), i32, two)}
+    out = _outputs(torch, out, shapes, params.device)
+    a = _slice_fields(_lib.WhatIfArgs(), params, Tq, spot, rate)
+    a.inst_u, a.inst_tau, a.inst_stride, a.inst_kind = _ptr(inst_u), _ptr(inst_tau), (0 if inst_u.dim() == 1 else nH), _ptr(inst_kind)
+    a.strike_mode, a.nH, a.lag, a.window, a.tail_probs, a.nL, a.min_scen = int(strike_mode), nH, lag, window, _doubles(tp), nL, min_scen
+    a.nQ, a.size, a.size_stride, a.stages, a.scen_per_wg = nQ, _ptr(size), (0 if size.dim() == 2 else nH * nQ), stages, int(scen_per_wg)
+    a.pnl, a.scen_flags = _ptr(pnl), _ptr(scen_flags)
+    for k in shapes:
+        setattr(a, k, _ptr(out[k]))
+    _call(torch, "ivs_svi_whatif_f64", a, stream, params, Tq, spot, inst_u, inst_tau, inst_kind, pnl, scen_flags, size, *out.values())
+    return {k: out[k] for k in shapes}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

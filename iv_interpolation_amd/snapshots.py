@@ -343,6 +343,38 @@ class HedgeReport:
     es: object                       # [B, nL]
 
 
+@dataclass
+class WhatIfReport:
+    """One underlying's what-if VaR and expected shortfall of a book per candidate trade and size at every snapshot (rules W0-W9).
+    The value arrays are device tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    lag: int
+    window: int
+    tail_probs: np.ndarray           # [nL]
+    min_scenarios: int
+    sizes: np.ndarray                # [nQ] the ladder as it was asked for
+    size_unit: str                   # "solo": multiples of the candidate's own minimum-variance size; "abs": quantities
+    labels: List[str]                # [nH] the candidates' names
+    strikes: np.ndarray              # [nH], NaN for the underlying
+    expiries: pd.DatetimeIndex       # [nH], NaT for the underlying
+    kind: np.ndarray                 # [nH] uint8: 0 call, 1 put, 2 the underlying
+    size: object                     # [B, nH, nQ] the quantity to ADD at every rung
+    inst_pnl: object                 # [B, window, nH] the scenario P&L of one unit of every candidate
+    inst_value: object               # [B, nH] the candidates' prices
+    trade_flags: object              # [B, nH] int32: IVS_HG_NEG_VOL or 0
+    var_w: object                    # [B, nH, nQ, nL] of the book with the trade; losses are positive
+    es_w: object                     # [B, nH, nQ, nL]
+    worst_w: object                  # [B, nH, nQ] int32
+    best: object                     # [B, nH, nL] int32: the rung with the smallest ES, -1 = none
+    var0: object                     # [B, nL] of the book as it is, formed by the same call
+    es0: object                      # [B, nL]
+    worst0: object                   # [B] int32
+    n_scen: object                   # [B] int32
+    var: object                      # [B, nL] the VarReport's
+    es: object                       # [B, nL]
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -432,6 +464,14 @@ class HipBackend:
         return engine.svi_hedge(params, d(Tq), spot, rate, d(inst_u), d(inst_tau), self._up(inst_kind, np.uint8), pnl, scen_flags, lag=lag,
                                 window=window, tail_probs=tail_probs, min_scen=min_scen, rounds=rounds, n_forced=n_forced, tol=tol,
                                 min_gain=min_gain, strike_mode=strike_mode, stream=self.stream)
+
+    def whatif(self, params, Tq, spot, rate, inst_u, inst_tau, inst_kind, pnl, scen_flags, size, lag, window, tail_probs, min_scen,
+               strike_mode, inst_pnl=None):
+        d = lambda a: self._up(a, np.float64)  # noqa: E731
+        return engine.svi_whatif(params, d(Tq), spot, rate, d(inst_u), d(inst_tau), self._up(inst_kind, np.uint8), pnl, scen_flags,
+                                 size if hasattr(size, "is_cuda") else d(size), inst_pnl=inst_pnl, lag=lag, window=window,
+                                 tail_probs=tail_probs, min_scen=min_scen, strike_mode=strike_mode, stream=self.stream,
+                                 stages=0 if inst_pnl is None else 2)
 
 
 def _host(a):
@@ -895,20 +935,78 @@ class SnapshotSurfaceBuilder:
             inst = instruments if instruments is not None else default_instruments(book, float(np.nanmedian(_host(r.spot))) if len(r.dates) else np.nan)
             if not 0 <= n_forced <= min(rounds, len(inst)):
                 raise ValueError(f"n_forced {n_forced!r} exceeds min(rounds, instruments) = {min(rounds, len(inst))}")
-            side = inst["callput"].astype(str).str.lower().str[:1]
-            if not side.isin(["c", "p", "u"]).all():
-                raise ValueError("an instrument's callput must start with c or p, or be `underlying`")
-            kind = np.where(side == "u", 2, np.where(side == "p", 1, 0)).astype(np.uint8)
-            strikes = np.where(kind == 2, np.nan, pd.to_numeric(inst["strike"], errors="coerce").to_numpy(np.float64))
-            expiry = pd.DatetimeIndex(pd.to_datetime(inst["expiry"]))
-            tau = self._tau(expiry, r.dates)
-            u = np.ascontiguousarray(np.broadcast_to(strikes, tau.shape))
+            kind, strikes, expiry, u, tau = self._instruments(inst, r.dates)
             g = be.hedge(v.params, r.tenors, r.spot, float(rate), u, tau, kind, h.pnl, h.scen_flags, lag, window, tp, min_scenarios, rounds,
                          int(n_forced), tol, min_gain, 1)
             reports.append(HedgeReport(r.underlying, r.dates, lag, window, np.asarray(tp, np.float64), min_scenarios, rounds, int(n_forced), tol,
                                        min_gain, [str(x) for x in inst["symbol"]], strikes, expiry, kind, g["inst_pnl"], g["inst_flags"], g["pick"],
                                        g["ss"], g["n_rounds"], g["hedge"], g["pnl_hedged"], g["var_h"], g["es_h"], g["worst_h"], g["n_scen"],
                                        g["solo_qty"], g["solo_left"], g["inst_value"], h.var, h.es))
+        return reports
+
+    def _instruments(self, inst: pd.DataFrame, dates):
+        """kind [nH] uint8, strikes [nH], expiries [nH] and the queries u, tau [B, nH] of a frame of candidate instruments."""
+        side = inst["callput"].astype(str).str.lower().str[:1]
+        if not side.isin(["c", "p", "u"]).all():
+            raise ValueError("an instrument's callput must start with c or p, or be `underlying`")
+        kind = np.where(side == "u", 2, np.where(side == "p", 1, 0)).astype(np.uint8)
+        strikes = np.where(kind == 2, np.nan, pd.to_numeric(inst["strike"], errors="coerce").to_numpy(np.float64))
+        expiry = pd.DatetimeIndex(pd.to_datetime(inst["expiry"]))
+        tau = self._tau(expiry, dates)
+        return kind, strikes, expiry, np.ascontiguousarray(np.broadcast_to(strikes, tau.shape)), tau
+
+    # ------------------------------------------------------------------ what-if
+    def whatif(self, results: Sequence[SnapshotSurfaces], book: pd.DataFrame, instruments: Optional[pd.DataFrame] = None,
+               sizes=(0.25, 0.5, 0.75, 1.0, 1.25, 1.5, 2.0, 3.0), size_unit: str = "solo", var_reports=None, svi_reports=None,
+               rate: float = 0.0, lag: int = 1, window: int = 256, tail_probs=(0.05, 0.01), min_scenarios: int = 20,
+               fit_rounds: int = 0) -> List["WhatIfReport"]:
+        """What the VaR and expected shortfall of var() become when a candidate trade is added to the book (rules W0-W9): one
+        WhatIfReport per underlying with, per snapshot, instrument and rung of the ladder `sizes` (at most 16), the tail figures of
+        the book with the trade, and per instrument the rung with the smallest ES.  size_unit "solo": a rung is that multiple of the
+        instrument's own minimum-variance size (hedge()'s solo_qty at that snapshot; an instrument without one has no live rung);
+        "abs": the rungs are quantities.  instruments, var_reports, svi_reports and fit_rounds as for hedge()."""
+        from .engine import whatif_settings
+        if size_unit not in ("solo", "abs"):
+            raise ValueError(f"size_unit {size_unit!r} is neither 'solo' nor 'abs'")
+        if instruments is not None:
+            for c in ("symbol", "strike", "expiry", "callput"):
+                if c not in instruments.columns:
+                    raise KeyError(c)
+        mult = np.asarray(sizes, np.float64).reshape(-1)
+        svi_reports, _, _, _, _, own = self._book(
+            book, (results, svi_reports, rate, fit_rounds),
+            settings=lambda: whatif_settings(lag, window, tail_probs, min_scenarios, _HG_MAX_INST if instruments is None else len(instruments),
+                                             len(mult)))
+        lag, window, tp, min_scenarios, _, _ = own
+        if var_reports is None:
+            var_reports = self.var(results, book, svi_reports, rate, lag, window, tp, min_scenarios)
+        if len(var_reports) != len(results):
+            raise ValueError(f"{len(var_reports)} VaR reports for {len(results)} surfaces")
+        be = self._backend or HipBackend()
+        reports = []
+        for r, v, h in zip(results, svi_reports, var_reports):
+            if (h.lag, h.window, h.min_scenarios) != (lag, window, min_scenarios) or list(h.tail_probs) != list(tp):
+                raise ValueError("the VaR reports were made with other settings (lag, window, tail_probs, min_scenarios)")
+            inst = instruments if instruments is not None else default_instruments(book, float(np.nanmedian(_host(r.spot))) if len(r.dates) else np.nan)
+            kind, strikes, expiry, u, tau = self._instruments(inst, r.dates)
+            args = (v.params, r.tenors, r.spot, float(rate), u, tau, kind, h.pnl, h.scen_flags)
+            if size_unit == "solo":                          # section 21 sizes the ladder, and its rows serve the ladder as they are
+                g = be.hedge(*args, lag, window, tp, min_scenarios, 1, 0, 1e-6, 1e-4, 1)
+                solo = g["solo_qty"]
+                if hasattr(solo, "is_cuda"):
+                    size = (solo[:, :, None] * solo.new_tensor(mult)).contiguous()
+                else:
+                    size = np.ascontiguousarray(np.asarray(solo)[:, :, None] * mult)
+                w = be.whatif(*args, size, lag, window, tp, min_scenarios, 1, inst_pnl=g["inst_pnl"])
+                w = dict(w, inst_value=g["inst_value"])
+            else:
+                size = np.ascontiguousarray(np.broadcast_to(mult, (len(kind), len(mult))))
+                w = be.whatif(*args, size, lag, window, tp, min_scenarios, 1)
+                size = np.broadcast_to(size, (len(r.dates),) + size.shape)
+            reports.append(WhatIfReport(r.underlying, r.dates, lag, window, np.asarray(tp, np.float64), min_scenarios, mult, size_unit,
+                                        [str(x) for x in inst["symbol"]], strikes, expiry, kind, size, w["inst_pnl"], w["inst_value"],
+                                        w["trade_flags"], w["var_w"], w["es_w"], w["worst_w"], w["best"], w["var0"], w["es0"], w["worst0"],
+                                        w["n_scen"], h.var, h.es))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -1539,6 +1637,48 @@ def hedge_frame(reports: Sequence[HedgeReport], snapshots: Sequence[SnapshotSurf
                              "instrument": pd.Series(dtype=object), "quantity": f64, "left": f64})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date", "round"], kind="stable").reset_index(drop=True)
+
+
+def whatif_frame(reports: Sequence[WhatIfReport], snapshots: Sequence[SnapshotSurfaces], top: int = 5) -> pd.DataFrame:
+    """Per snapshot with quotes > 0 the `top` instruments by the reduction of the ES at the first tail probability, each at its
+    best rung there, ordered by (underlying, date, that reduction, largest first): columns underlying, date, instrument, size (the
+    quantity to ADD), per tail probability var_<tp> / es_<tp> of the book, var_<tp>_after / es_<tp>_after with the trade and
+    var_<tp>_change / es_<tp>_change (after - before; losses are positive, so a negative change is an improvement), and
+    worst_start / worst_start_after (the first snapshot of the worst scenario's pair before and with the trade).  Instruments
+    without a live rung are left out."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        nL = len(p.tail_probs)
+        if not nL or not len(keep) or not len(p.labels):
+            continue
+        best = _host(p.best)[keep][:, :, 0].astype(np.int64)                                # [n, nH]
+        jj = np.maximum(best, 0)
+        at = lambda a: np.take_along_axis(_host(a)[keep], jj.reshape(jj.shape + (1,) * (_host(a).ndim - 2)), axis=2)[:, :, 0]  # noqa: E731
+        var_b, es_b, worst_b, size_b = at(p.var_w), at(p.es_w), at(p.worst_w).astype(np.int64), at(np.broadcast_to(_host(p.size), _host(p.var_w).shape[:3]))
+        var0, es0, worst0 = _host(p.var0)[keep], _host(p.es0)[keep], _host(p.worst0)[keep].astype(np.int64)
+        with np.errstate(all="ignore"):
+            gain = np.where(best >= 0, es0[:, :1] - es_b[:, :, 0], -np.inf)
+        order = np.argsort(-gain, axis=1, kind="stable")[:, :max(int(top), 0)]
+        rows = np.repeat(np.arange(len(keep)), order.shape[1])
+        c = order.ravel()
+        ok = best[rows, c] >= 0
+        rows, c = rows[ok], c[ok]
+        start = lambda w: pd.DatetimeIndex(p.dates[np.where(w >= 0, keep[rows] - p.lag - w, 0)]).where(w >= 0)      # noqa: E731  H0
+        cols = {"underlying": p.underlying, "date": p.dates[keep][rows], "instrument": np.asarray(p.labels, object)[c], "size": size_b[rows, c]}
+        for n, tp in enumerate(p.tail_probs):
+            for k, before, after in (("var", var0, var_b), ("es", es0, es_b)):
+                name = f"{k}_{float(tp):g}"
+                cols[name], cols[name + "_after"] = before[rows, n], after[rows, c, n]
+                cols[name + "_change"] = after[rows, c, n] - before[rows, n]
+        cols["worst_start"], cols["worst_start_after"] = start(worst0[rows]), start(worst_b[rows, c])
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64, ns = pd.Series(dtype=np.float64), pd.Series(dtype="datetime64[ns]")
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": ns, "instrument": pd.Series(dtype=object), "size": f64,
+                             "worst_start": ns, "worst_start_after": ns})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
 
 
 def top_contributors(reports: Sequence[VarAttributionReport], snapshots: Sequence[SnapshotSurfaces], level: int = 0, count: int = 10) -> pd.DataFrame:
