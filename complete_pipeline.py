@@ -41,6 +41,7 @@ VAR_TABLE = "iv_var"
 VAR_ATTRIB_TABLE = "iv_var_attrib"
 HEDGE_TABLE = "iv_hedge"
 WHATIF_TABLE = "iv_whatif"
+VAR_CI_TABLE = "iv_var_ci"
 SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
@@ -691,6 +692,42 @@ class CompleteOptimizedPipeline:
         print(f"WHAT-IF COMPLETE: {rows[0]:,} rows; median ES reduction of the best trade: {gain:.3%}")
         return {**result, "success": result["success"] and rows[0] > 0, "whatif_rows": rows[0], "median_es_reduction": gain}
 
+    def run_varci(self, book_file: Optional[str] = None, lag: int = 1, window: int = 256, levels=(0.05, 0.01), min_scenarios: int = 20,
+                  replicates: int = 512, block: Optional[int] = None, seed: int = 0, ci=(0.05, 0.95)) -> dict:
+        """Bootstrap confidence of the VaR and ES: run_var, then per snapshot the standard error and an interval
+        of every tail figure over `replicates` resamples of its valid scenarios, in circular blocks of `block` scenarios (None: the
+        lag, the overlap of the scenarios), on the device.  ci: the probabilities of the interval's ends.  One `iv_var_ci` table per
+        underlying (confidence_frame's columns) besides run_var's `iv_var`.  The result has run_var's keys plus ci_rows and
+        median_rel_se: per level the median of se / VaR over the snapshots with a finite VaR."""
+        from iv_interpolation_amd.engine import bootstrap_settings
+        from iv_interpolation_amd.snapshots import confidence_frame
+        try:
+            bootstrap_settings(window, levels, min_scenarios, replicates, max(1, int(lag)) if block is None else block, seed, ci)
+        except (ValueError, TypeError) as e:
+            return {"success": False, "error": str(e)}
+        rows, tables = [0], []
+
+        def confidence(builder, res, held, fit, reports):
+            rep = builder.var_confidence(reports, n_rep=replicates, block=block, seed=seed, ci=ci)
+            table = confidence_frame(rep, [res])
+            self.store.write_table(VAR_CI_TABLE, res.underlying, table)
+            rows[0] += len(table)
+            tables.append(table)
+            print(f"  {res.underlying}: {len(table)} confidence rows, {rep[0].n_rep} replicates in blocks of {rep[0].block}")
+        result = self._var_stage(book_file, lag, window, levels, min_scenarios, each=confidence)
+        if "error" in result:
+            return result
+        rel = []
+        for tp in levels:
+            name = f"var_{float(tp):g}"
+            var = np.concatenate([t[name].to_numpy(np.float64) for t in tables]) if tables else np.zeros(0)
+            se = np.concatenate([t[name + "_se"].to_numpy(np.float64) for t in tables]) if tables else np.zeros(0)
+            ok = np.isfinite(var)
+            with np.errstate(all="ignore"):
+                rel.append(float(np.nanmedian((se / var)[ok])) if ok.any() else float("nan"))
+        print(f"VAR CONFIDENCE COMPLETE: {rows[0]:,} rows; median se / VaR: " + ", ".join(f"tp {float(tp):g}: {x:.1%}" for tp, x in zip(levels, rel)))
+        return {**result, "success": result["success"] and rows[0] > 0, "ci_rows": rows[0], "median_rel_se": rel}
+
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
         quantiles, level probabilities and tails of every tenor row on the device, and one `iv_distribution` table per
@@ -871,7 +908,7 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "hedge", "whatif", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "hedge", "whatif", "varci", "all"], default="all")
     parser.add_argument("--book", metavar="FILE", help="--task risk / explain / var: a CSV of symbol, quantity (default: every listed contract, +1 each)")
     parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain / var: the pair is snapshot p and snapshot p + N (default 1)")
     parser.add_argument("--window", type=int, default=256, metavar="W", help="--task var: scenarios kept per snapshot (default 256)")
@@ -883,6 +920,10 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
     parser.add_argument("--sizes", default="0.25,0.5,0.75,1,1.25,1.5,2,3", metavar="LIST", help="--task whatif: the ladder of sizes, at most 16 (default 0.25,...,3)")
     parser.add_argument("--size-unit", choices=["solo", "abs"], default="solo", help="--task whatif: sizes are multiples of a candidate's own minimum-variance size, or quantities (default solo)")
     parser.add_argument("--top", type=int, default=5, metavar="N", help="--task whatif: trades kept per snapshot (default 5)")
+    parser.add_argument("--replicates", type=int, default=512, metavar="R", help="--task varci: bootstrap replicates per snapshot, 1..1024 (default 512)")
+    parser.add_argument("--block", type=int, default=None, metavar="L", help="--task varci: scenarios per block of the circular block bootstrap (default: the lag)")
+    parser.add_argument("--seed", type=int, default=0, metavar="S", help="--task varci: the seed of the resampling (default 0)")
+    parser.add_argument("--ci", default="0.05,0.95", metavar="P,P", help="--task varci: the probabilities of the interval's ends (default 0.05,0.95)")
     parser.add_argument("--group-by", choices=["expiry", "side"], default="expiry", help="--task varattrib: the groups the VaR is attributed to (default expiry)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
@@ -952,6 +993,9 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
             elif args.task == "whatif":
                 result = pipeline.run_whatif(args.book, args.trades, [float(x) for x in args.sizes.split(",") if x.strip()], args.size_unit, args.top,
                                              args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios)
+            elif args.task == "varci":
+                result = pipeline.run_varci(args.book, args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios,
+                                            args.replicates, args.block, args.seed, [float(x) for x in args.ci.split(",") if x.strip()])
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

@@ -1049,6 +1049,57 @@ typedef struct ivs_whatif_args {
 int ivs_svi_whatif_f64(const ivs_whatif_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Bootstrap standard errors and intervals for a book's VaR and expected shortfall (rules C0-C9; additive to
+ * ABI 5): how far the tail figures of ivs_svi_hsim_f64 move when the row of scenario P&Ls is resampled.  The call works on rows
+ * alone: pnl and scen_flags [B][window] as an ivs_svi_hsim_f64 call wrote them (INPUTS; any rows with that meaning, the hedged row of
+ * ivs_svi_hedge_f64 for one); no slices, no book, no lag.  The ranked scenarios, their order (ascending, ties to the lower s) and n
+ * are ivs_svi_hsim_f64's; the ranked scenarios in ascending s are the time positions 0..n-1.  A row is active iff n >= min_scen,
+ * n > 0 and every ranked value is finite.  Replicate r of n_rep is a circular block bootstrap: ceil(n / L') blocks of L' = min(block, n)
+ * consecutive positions (mod n), each starting at (u n) >> 32 for the upper word u of a splitmix64 finaliser at the counter
+ * (r << 32 | block index) and `seed`, laid end to end and cut at n draws.  A replicate's VaR and ES are ivs_svi_hsim_f64's on the
+ * drawn values: m = max(1, floor(n x tp)); up the ranks, each drawn rank adds (double)k x v with k = min(its count, what is left of m),
+ * serially from +0.0; 0.0 - the value at which m is reached and 0.0 - sum / m.
+ *   var0, es0 [B][nL], n_scen [B] (int32)   ivs_svi_hsim_f64's var, es and n_valid of the row itself, formed here (the same bits).
+ *   mean, variance [B][2][nL]               over the n_rep replicate values of statistic 0 = VaR, 1 = ES at every level: the sum in the
+ *                                           order of rule B5 over the replicates (passes of 256) / n_rep, and the sum of the rounded
+ *                                           squares of (value - mean) in the same order / (n_rep - 1) (NaN for n_rep = 1).
+ *   quant [B][2][nL][nC]                    the i-th smallest (from 0) of the replicate values, i = min(n_rep - 1, floor(n_rep x ci)).
+ *   rep [B][n_rep][2][nL]                   the replicate values themselves.  May be NULL; the call then keeps them in the workspace.
+ * A row that is not active has NaN in mean, variance, quant and rep.  The bits of a row's outputs depend on the row, tail_probs,
+ * min_scen, block, seed, ci_probs and n_rep alone, and rep[p][r] on n_rep only through r < n_rep.
+ *
+ * workspace: ivs_hsim_bootstrap_workspace_bytes(B, n_rep, nL) bytes of device memory, 8-byte aligned, when rep is NULL; with rep given
+ * none is needed (NULL, 0).  That function returns 0 for sizes the call refuses.
+ * IVS_EINVAL: null args, a negative size, a null required pointer (tail_probs with nL > 0, ci_probs with nC > 0, pnl, scen_flags,
+ * n_scen, and with nL > 0 var0, es0, mean, variance, with nC > 0 also quant), a workspace that is missing or too small.  IVS_ERANGE:
+ * window outside 1..1024, nL > 8, a tail probability outside (0, 1), min_scen < 1, n_rep or block outside 1..1024, nC > 8, an
+ * interval probability that is not finite and inside (0, 1), B*window, B*n_rep*2*max(nL,1) or B*2*max(nL,1)*max(nC,1) >= 2^31.  The
+ * limits are checked before the zero-size return; B == 0 is a no-op.  A refused call launches nothing and touches no buffer.  No
+ * allocation, no synchronisation (capturable), no dynamic LDS; ONE launch.
+ */
+typedef struct ivs_bootstrap_args {
+    const double* pnl;         /* [B][window], input */
+    const int32_t* scen_flags; /* [B][window], input */
+    int64_t B;
+    int32_t window;            /* 1..1024 */
+    int32_t nL;                /* 0..8 */
+    const double* tail_probs;  /* host */
+    int32_t min_scen;          /* >= 1 */
+    int32_t n_rep;             /* 1..1024 */
+    int32_t block;             /* 1..1024 */
+    int32_t nC;                /* 0..8 */
+    uint64_t seed;
+    const double* ci_probs;    /* host, each inside (0, 1) */
+    double* var0; double* es0; /* [B][nL] */
+    int32_t* n_scen;           /* [B] */
+    double* mean; double* variance; /* [B][2][nL] */
+    double* quant;             /* [B][2][nL][nC] */
+    double* rep;               /* [B][n_rep][2][nL], may be NULL */
+} ivs_bootstrap_args;
+size_t ivs_hsim_bootstrap_workspace_bytes(int64_t B, int32_t n_rep, int32_t nL);
+int ivs_hsim_bootstrap_f64(const ivs_bootstrap_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -1137,7 +1188,8 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
 /* name of the kernel the last ivs_surface_batch_f64 / ivs_snapshot_assemble_f64 / ivs_smile_delta_points_f64 /
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
  * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64,
- * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64, ivs_svi_hsim_attrib_f64, ivs_svi_hedge_f64 and ivs_svi_whatif_f64 set it too */
+ * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64, ivs_svi_hsim_attrib_f64, ivs_svi_hedge_f64,
+ * ivs_svi_whatif_f64 and ivs_hsim_bootstrap_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

@@ -41,6 +41,7 @@ HG_DEAD, HG_NEG_VOL, HG_FLAT, HG_SPENT, HG_CHOSEN = 1, 2, 4, 8, 16
 HG_MAX_INST, HG_MAX_ROUNDS = 64, 8
 HG_CALL, HG_PUT, HG_UNDERLYING = 0, 1, 2                         # inst_kind
 WI_MAX_RUNGS = 16                                                # sizes per candidate of the what-if ladder
+BOOT_MAX_REP, BOOT_MAX_BLOCK, BOOT_MAX_CI = 1024, 1024, 8        # replicates, block length and interval probabilities of the bootstrap
 # IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
@@ -244,6 +245,14 @@ class WhatIfArgs(C.Structure):
                 ("var_w", _p), ("es_w", _p), ("worst_w", _p), ("best", _p), ("var0", _p), ("es0", _p), ("worst0", _p), ("n_scen", _p)]
 
 
+class BootstrapArgs(C.Structure):
+    """ivs_bootstrap_args of include/ivs.h (field for field)."""
+    _fields_ = [("pnl", _p), ("scen_flags", _p), ("B", _i64), ("window", _i32), ("nL", _i32),
+                ("tail_probs", C.POINTER(C.c_double)), ("min_scen", _i32), ("n_rep", _i32), ("block", _i32), ("nC", _i32),
+                ("seed", C.c_uint64), ("ci_probs", C.POINTER(C.c_double)),
+                ("var0", _p), ("es0", _p), ("n_scen", _p), ("mean", _p), ("variance", _p), ("quant", _p), ("rep", _p)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -297,6 +306,8 @@ SIGNATURES = {
     "ivs_svi_hsim_attrib_f64": (C.c_int, [C.POINTER(HsimAttribArgs), _p, _sz, _p]),
     "ivs_svi_hedge_f64": (C.c_int, [C.POINTER(HedgeArgs), _p, _sz, _p]),
     "ivs_svi_whatif_f64": (C.c_int, [C.POINTER(WhatIfArgs), _p, _sz, _p]),
+    "ivs_hsim_bootstrap_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ivs_hsim_bootstrap_f64": (C.c_int, [C.POINTER(BootstrapArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "ivs_arbitrage.hpp"
+#include "ivs_bootstrap.hpp"
 #include "ivs_bridge.hpp"
 #include "ivs_candles.hpp"
 #include "ivs_dispatch.hpp"
@@ -610,6 +611,54 @@ int ivs_svi_whatif_f64(const ivs_whatif_args* a, void*, size_t, void* stream) {
         return end_call("whatif_tail_kernel");
     }
     return IVS_OK;
+}
+
+// elements of replicate values per call: what rep, or the workspace in its place, holds
+static int64_t bootstrap_rep_elems(int64_t B, int32_t n_rep, int32_t nL) { return B * n_rep * 2 * nL; }
+
+size_t ivs_hsim_bootstrap_workspace_bytes(int64_t B, int32_t n_rep, int32_t nL) {
+    if (B <= 0 || n_rep < 1 || n_rep > ivs::BT_MAX_REP || nL < 1 || nL > ivs::HS_MAX_LEVELS || B > 0x7fffffffLL / ((int64_t)n_rep * 2 * nL)) return 0;
+    return (size_t)bootstrap_rep_elems(B, n_rep, nL) * sizeof(double);
+}
+
+int ivs_hsim_bootstrap_f64(const ivs_bootstrap_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "ivs_hsim_bootstrap_f64";
+    if (int rc = begin_call(fn, a)) return rc;
+    if (a->B < 0 || a->nL < 0 || a->nC < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->window < 1 || a->window > ivs::HS_MAX_WINDOW)
+        return fail(IVS_ERANGE, "%s: window=%d outside [1,%d]", fn, a->window, ivs::HS_MAX_WINDOW);
+    if (a->nL > ivs::HS_MAX_LEVELS) return fail(IVS_ERANGE, "%s: nL=%d > %d tail probabilities", fn, a->nL, ivs::HS_MAX_LEVELS);
+    if (a->nL > 0 && !a->tail_probs) return fail(IVS_EINVAL, "%s: null tail probabilities", fn);
+    for (int l = 0; l < a->nL; ++l)
+        if (!(a->tail_probs[l] > 0.0 && a->tail_probs[l] < 1.0))
+            return fail(IVS_ERANGE, "%s: tail probability %d (%g) is not inside (0, 1)", fn, l, a->tail_probs[l]);
+    if (a->min_scen < 1) return fail(IVS_ERANGE, "%s: min_scen=%d < 1", fn, a->min_scen);
+    if (a->n_rep < 1 || a->n_rep > ivs::BT_MAX_REP) return fail(IVS_ERANGE, "%s: n_rep=%d outside [1,%d]", fn, a->n_rep, ivs::BT_MAX_REP);
+    if (a->block < 1 || a->block > ivs::BT_MAX_BLOCK) return fail(IVS_ERANGE, "%s: block=%d outside [1,%d]", fn, a->block, ivs::BT_MAX_BLOCK);
+    if (a->nC > ivs::BT_MAX_CI) return fail(IVS_ERANGE, "%s: nC=%d > %d interval probabilities", fn, a->nC, ivs::BT_MAX_CI);
+    if (a->nC > 0 && !a->ci_probs) return fail(IVS_EINVAL, "%s: null interval probabilities", fn);
+    for (int c = 0; c < a->nC; ++c)
+        if (!(a->ci_probs[c] > 0.0 && a->ci_probs[c] < 1.0))
+            return fail(IVS_ERANGE, "%s: interval probability %d (%g) is not inside (0, 1)", fn, c, a->ci_probs[c]);
+    const int64_t nl1 = a->nL > 0 ? a->nL : 1, nc1 = a->nC > 0 ? a->nC : 1;
+    if (a->B > 0x7fffffffLL / a->window || a->B > 0x7fffffffLL / ((int64_t)a->n_rep * 2 * nl1) || a->B > 0x7fffffffLL / (2 * nl1 * nc1))
+        return fail(IVS_ERANGE, "%s: %lld rows x %d scenarios, x %d replicates or x %d quantiles at %d levels exceed one launch", fn,
+                    (long long)a->B, a->window, a->n_rep, a->nC, a->nL);
+    if (a->B == 0) return IVS_OK;                                                                  // C9
+    if (!a->pnl || !a->scen_flags || !a->n_scen || (a->nL > 0 && (!a->var0 || !a->es0 || !a->mean || !a->variance || (a->nC > 0 && !a->quant))))
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    const size_t need = (size_t)bootstrap_rep_elems(a->B, a->n_rep, a->nL) * sizeof(double);
+    if (!a->rep && need > 0 && (!workspace || workspace_bytes < need))
+        return fail(IVS_EINVAL, "%s: workspace of %zu bytes, %zu needed without rep", fn, workspace ? workspace_bytes : (size_t)0, need);
+    ivs::BootParams p{};
+    p.pnl = a->pnl; p.scen_flags = a->scen_flags; p.window = a->window; p.nL = a->nL; p.min_scen = a->min_scen;
+    p.R = a->n_rep; p.L = a->block; p.nC = a->nC; p.seed = a->seed;
+    for (int l = 0; l < a->nL; ++l) p.tp[l] = a->tail_probs[l];
+    for (int c = 0; c < a->nC; ++c) p.ci[c] = a->ci_probs[c];
+    p.var0 = a->var0; p.es0 = a->es0; p.n_scen = a->n_scen; p.mean = a->mean; p.variance = a->variance; p.quant = a->quant;
+    p.rep = a->rep ? a->rep : static_cast<double*>(workspace);          // C9: the one way through global memory
+    hipLaunchKernelGGL(ivs::hsim_bootstrap_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
+    return end_call("hsim_bootstrap_kernel");
 }
 
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void*, size_t, void* stream) {

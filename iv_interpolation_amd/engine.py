@@ -1047,6 +1047,75 @@ def svi_whatif(params, Tq, spot, rate, inst_u, inst_tau, inst_kind, pnl, scen_fl
     return {k: out[k] for k in shapes}
 
 
+BOOTSTRAP_OUTPUTS = ("var0", "es0", "n_scen", "mean", "variance", "se", "quant", "rep")
+DEFAULT_CI_PROBS = (0.05, 0.95)
+
+
+def bootstrap_settings(window, tail_probs, min_scen, n_rep, block, seed, ci_probs):
+    """The host-side checks of a bootstrap: window, tail_probs and min_scen as hsim_settings has them,
+    n_rep and block integers in 1..1024, seed an integer in 0..2^64 - 1, at most 8 interval probabilities, each finite and inside
+    (0, 1); ValueError otherwise.  Returns (window, tail_probs as a list, min_scen, n_rep, block, seed, ci_probs as a list)."""
+    import math
+    _, window, tp, min_scen, _ = hsim_settings(1, window, tail_probs, min_scen)
+    for name, v, hi in (("n_rep", n_rep, _lib.BOOT_MAX_REP), ("block", block, _lib.BOOT_MAX_BLOCK)):
+        if int(v) != v or not 1 <= v <= hi:
+            raise ValueError(f"{name} {v!r} is not an integer in 1..{hi}")
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed {seed!r} is not an integer in 0..2^64 - 1")
+    ci = [float(x) for x in ci_probs]
+    if len(ci) > _lib.BOOT_MAX_CI:
+        raise ValueError(f"{len(ci)} interval probabilities: at most {_lib.BOOT_MAX_CI} are supported")
+    if any(not (math.isfinite(x) and 0.0 < x < 1.0) for x in ci):
+        raise ValueError(f"interval probabilities must be finite and inside (0, 1), got {ci!r}")
+    return window, tp, min_scen, int(n_rep), int(block), int(seed), ci
+
+
+def hsim_bootstrap(pnl, scen_flags, tail_probs=DEFAULT_TAIL_PROBS, min_scen: int = 20, n_rep: int = 512, block: int = 1, seed: int = 0,
+                   ci_probs=DEFAULT_CI_PROBS, want_rep: bool = False, out=None, stream=None):
+    """Bootstrap standard errors and intervals for the VaR and expected shortfall of rows of scenario P&Ls (ivs_hsim_bootstrap_f64;
+    rules C0-C9 of DESIGN.md section 23).  pnl float64 and scen_flags int32 [B, window] as svi_hsim returns them (or svi_hedge's
+    pnl_hedged with the same flags).  Every row is ranked once; each of n_rep replicates draws n of its ranked scenarios again, in
+    circular blocks of `block` consecutive ones in time order (block = the lag of overlapping scenarios keeps their dependence),
+    and takes svi_hsim's VaR and ES of the draw.  bootstrap_settings has the limits.
+    want_rep: whether to return the replicate values themselves [B, n_rep, 2, nL] (None otherwise; a workspace of that size is
+    then allocated for the call).  `out`: optional dict of preallocated outputs (se is never one: it is formed from variance).
+    Returns dict(var0, es0 [B,nL] and n_scen int32 [B]: svi_hsim's var, es and n_valid of the rows; mean, variance, se [B,2,nL] over
+    the replicates, statistic 0 = VaR and 1 = ES, se = sqrt(variance); quant [B,2,nL,nC]: the replicates' quantiles at ci_probs;
+    rep) of device tensors.  A row with fewer than min_scen ranked scenarios, or an infinite one, has NaN in all but the first three."""
+    torch = require_device()
+    pnl = _f64(torch, pnl, "pnl")
+    if not scen_flags.is_cuda or scen_flags.dtype != torch.int32:
+        raise TypeError("scen_flags must be a CUDA int32 tensor")
+    scen_flags = scen_flags.contiguous()
+    if pnl.dim() != 2 or tuple(scen_flags.shape) != tuple(pnl.shape):
+        raise ValueError("pnl and scen_flags must be [B, window], of one shape")
+    B, window = pnl.shape
+    window, tp, min_scen, n_rep, block, seed, ci = bootstrap_settings(window, tail_probs, min_scen, n_rep, block, seed, ci_probs)
+    nL, nC = len(tp), len(ci)
+    if B * window >= 2 ** 31 or B * n_rep * 2 * max(nL, 1) >= 2 ** 31 or B * 2 * max(nL, 1) * max(nC, 1) >= 2 ** 31:
+        raise ValueError(f"{B} rows x {window} scenarios, x {n_rep} replicates or x {nC} quantiles at {nL} levels exceed one launch")
+    if out is not None and "se" in out:
+        raise ValueError("se is formed from variance by the wrapper: it is no output of the call")
+    i32, f64 = torch.int32, torch.float64
+    shapes = {"var0": ((B, nL), f64, True), "es0": ((B, nL), f64, True), "n_scen": ((B,), i32, True), "mean": ((B, 2, nL), f64, True),
+              "variance": ((B, 2, nL), f64, True), "quant": ((B, 2, nL, nC), f64, True), "rep": ((B, n_rep, 2, nL), f64, bool(want_rep))}
+    out = _outputs(torch, out, shapes, pnl.device)
+    lib = _lib.load()
+    ws_bytes = 0 if want_rep else int(lib.ivs_hsim_bootstrap_workspace_bytes(B, n_rep, nL))
+    ws = torch.empty(ws_bytes // 8, dtype=f64, device=pnl.device) if ws_bytes else None
+    a = _lib.BootstrapArgs()
+    a.pnl, a.scen_flags, a.B, a.window = _ptr(pnl), _ptr(scen_flags), B, window
+    a.tail_probs, a.nL, a.min_scen, a.n_rep, a.block, a.seed, a.ci_probs, a.nC = _doubles(tp), nL, min_scen, n_rep, block, seed, _doubles(ci), nC
+    for k in shapes:
+        setattr(a, k, _ptr(out[k]))
+    rc = lib.ivs_hsim_bootstrap_f64(a, _ptr(ws), ws_bytes, _stream(torch, stream))
+    _hold_for_stream(torch, stream, pnl, scen_flags, ws, *out.values())
+    _lib.check(rc, "ivs_hsim_bootstrap_f64")
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        se = torch.sqrt(out["variance"])                     # allocated on the stream that writes it
+    return {**{k: out[k] for k in shapes}, "se": se}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -375,6 +375,31 @@ class WhatIfReport:
     es: object                       # [B, nL]
 
 
+@dataclass
+class BootstrapReport:
+    """One underlying's bootstrap standard errors and intervals for the VaR and expected shortfall of a VarReport (rules C0-C9).
+    The value arrays are device tensors with the HIP backend (host arrays with an injected CPU backend).  Axis of size 2: 0 = VaR,
+    1 = ES."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    tail_probs: np.ndarray           # [nL]
+    min_scenarios: int
+    n_rep: int
+    block: int                       # scenarios per block of the circular block bootstrap
+    seed: int
+    ci: np.ndarray                   # [nC] the probabilities of the interval's ends
+    var0: object                     # [B, nL] the VarReport's var, formed again by the call
+    es0: object                      # [B, nL]
+    n_scen: object                   # [B] int32
+    mean: object                     # [B, 2, nL] over the replicates
+    variance: object                 # [B, 2, nL]
+    se: object                       # [B, 2, nL] sqrt(variance): the bootstrap standard error
+    quant: object                    # [B, 2, nL, nC] the replicates' quantiles at ci
+    var: object                      # [B, nL] the VarReport's
+    es: object                       # [B, nL]
+    n_valid: object                  # [B] int32
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -472,6 +497,10 @@ class HipBackend:
                                  size if hasattr(size, "is_cuda") else d(size), inst_pnl=inst_pnl, lag=lag, window=window,
                                  tail_probs=tail_probs, min_scen=min_scen, strike_mode=strike_mode, stream=self.stream,
                                  stages=0 if inst_pnl is None else 2)
+
+    def bootstrap(self, pnl, scen_flags, tail_probs, min_scen, n_rep, block, seed, ci_probs, want_rep=False):
+        return engine.hsim_bootstrap(pnl, scen_flags, tail_probs, min_scen, n_rep, block, seed, ci_probs, want_rep=want_rep,
+                                     stream=self.stream)
 
 
 def _host(a):
@@ -1007,6 +1036,25 @@ class SnapshotSurfaceBuilder:
                                         [str(x) for x in inst["symbol"]], strikes, expiry, kind, size, w["inst_pnl"], w["inst_value"],
                                         w["trade_flags"], w["var_w"], w["es_w"], w["worst_w"], w["best"], w["var0"], w["es0"], w["worst0"],
                                         w["n_scen"], h.var, h.es))
+        return reports
+
+    # ------------------------------------------------------------------ bootstrap confidence
+    def var_confidence(self, var_reports: Sequence["VarReport"], n_rep: int = 512, block: Optional[int] = None, seed: int = 0,
+                       ci=(0.05, 0.95)) -> List["BootstrapReport"]:
+        """How far the VaR and expected shortfall of var() can be trusted (rules C0-C9): one BootstrapReport per VarReport with,
+        per snapshot, statistic and level, the mean, the standard error and the quantiles `ci` of the statistic over n_rep
+        resamples of the snapshot's valid scenarios (a circular block bootstrap in time order).  block: scenarios per block;
+        None means max(1, lag), the overlap of the report's scenarios.  The rows are the reports' own: nothing is revalued."""
+        from .engine import bootstrap_settings
+        be = self._backend or HipBackend()
+        reports = []
+        for h in var_reports:
+            L = max(1, int(h.lag)) if block is None else block
+            _, tp, min_scen, R, L, sd, cis = bootstrap_settings(h.window, h.tail_probs, h.min_scenarios, n_rep, L, seed, ci)
+            q = be.bootstrap(h.pnl, h.scen_flags, tp, min_scen, R, L, sd, cis)
+            reports.append(BootstrapReport(h.underlying, h.dates, np.asarray(tp, np.float64), min_scen, R, L, sd, np.asarray(cis, np.float64),
+                                           q["var0"], q["es0"], q["n_scen"], q["mean"], q["variance"], q["se"], q["quant"], h.var, h.es,
+                                           h.n_valid))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -1548,6 +1596,29 @@ def var_frame(reports: Sequence[VarReport], snapshots: Sequence[SnapshotSurfaces
         f64, ns = pd.Series(dtype=np.float64), pd.Series(dtype="datetime64[ns]")
         return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": ns, "spot": f64, "n_valid": pd.Series(dtype=np.int32),
                              "worst_pnl": f64, "worst_start": ns, "value": f64, "gross": f64, "n_dead": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def confidence_frame(reports: Sequence[BootstrapReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per snapshot with quotes > 0, ordered by (underlying, date): columns underlying, date, n_valid and per tail
+    probability var_<tp>, var_<tp>_se, var_<tp>_lo, var_<tp>_hi, es_<tp>, es_<tp>_se, es_<tp>_lo, es_<tp>_hi: the VarReport's figure,
+    its bootstrap standard error and the replicates' quantiles at the first and the last of the report's ci (NaN without one)."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        cols = {"underlying": p.underlying, "date": p.dates[keep], "n_valid": _host(p.n_valid)[keep].astype(np.int32)}
+        se, quant = _host(p.se)[keep], _host(p.quant)[keep]
+        for n, tp in enumerate(p.tail_probs):
+            for k, (name, own) in enumerate((("var", p.var), ("es", p.es))):
+                col = f"{name}_{float(tp):g}"
+                cols[col] = _host(own)[keep][:, n]
+                cols[col + "_se"] = se[:, k, n]
+                cols[col + "_lo"] = quant[:, k, n, 0] if len(p.ci) else np.full(len(keep), np.nan)
+                cols[col + "_hi"] = quant[:, k, n, -1] if len(p.ci) else np.full(len(keep), np.nan)
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "n_valid": pd.Series(dtype=np.int32)})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
 
