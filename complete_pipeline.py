@@ -42,6 +42,7 @@ VAR_ATTRIB_TABLE = "iv_var_attrib"
 HEDGE_TABLE = "iv_hedge"
 WHATIF_TABLE = "iv_whatif"
 VAR_CI_TABLE = "iv_var_ci"
+VAR_W_TABLE = "iv_var_w"
 SCENARIO_TABLE = "iv_scenarios"
 PIPELINE_INLINE = 4                                     # engine strategy code of reference complete_pipeline.py:473-510
 
@@ -467,9 +468,10 @@ class CompleteOptimizedPipeline:
         below -VaR, exceedance_rate = their share (NaN without an eligible snapshot), to be read beside tp."""
         return self._var_stage(book_file, lag, window, levels, min_scenarios)
 
-    def _var_stage(self, book_file, lag, window, levels, min_scenarios, each=None) -> dict:
+    def _var_stage(self, book_file, lag, window, levels, min_scenarios, each=None, scored=None) -> dict:
         """The stage behind run_var and run_varattrib: run_var's work and result; each(builder, res, held, fit, reports), when
-        given, is called once per underlying with the VarReports just made, after its iv_var table is written."""
+        given, is called once per underlying with the VarReports just made, after its iv_var table is written; scored(res, both),
+        when given, once per underlying with the rows of the back-test: iv_var's columns beside `actual`."""
         from iv_interpolation_amd import _lib
         from iv_interpolation_amd.engine import hsim_settings
         from iv_interpolation_amd.snapshots import SnapshotSurfaceBuilder, explain_frame, var_frame
@@ -507,6 +509,8 @@ class CompleteOptimizedPipeline:
             realised = explain_frame(builder.explain([res], held, [fit], lag=lag), [res])
             both = table.merge(realised[["start", "actual"]], left_on="date", right_on="start", how="inner")
             actual = both["actual"].to_numpy(np.float64)
+            if scored is not None:
+                scored(res, both)
             for n, tp in enumerate(levels):
                 var = both[f"var_{tp:g}"].to_numpy(np.float64)
                 ok = np.isfinite(var) & np.isfinite(actual)
@@ -728,6 +732,58 @@ class CompleteOptimizedPipeline:
         print(f"VAR CONFIDENCE COMPLETE: {rows[0]:,} rows; median se / VaR: " + ", ".join(f"tp {float(tp):g}: {x:.1%}" for tp, x in zip(levels, rel)))
         return {**result, "success": result["success"] and rows[0] > 0, "ci_rows": rows[0], "median_rel_se": rel}
 
+    def run_varw(self, book_file: Optional[str] = None, lag: int = 1, window: int = 256, levels=(0.05, 0.01), min_scenarios: int = 20,
+                 decay: float = 0.99, vol_span: int = 0, vol_decay: float = 0.94, scale_cap: float = 3.0, min_returns: Optional[int] = None) -> dict:
+        """Age-weighted, volatility-scaled VaR and ES: run_var, then per snapshot the tail of the same scenarios
+        with the weight decay^s on the scenario of age s and, with vol_span > 0, every scenario scaled by the running vol of the spot
+        today over that at its start (the root of the vol_decay-weighted mean of vol_span squared returns, NaN before min_returns
+        of them, None: min(20, vol_span); the factor inside [1 / scale_cap, scale_cap]), on the device.  One `iv_var_w` table per underlying
+        (weighted_var_frame's columns) besides run_var's `iv_var`.  The result has run_var's keys plus w_rows, backtest_w (run_var's
+        back-test on the weighted VaR) and kupiec: per level dict(tp, plain, weighted) with Kupiec's likelihood ratio of the two
+        back-tests (kupiec_lr), to be read against chi-squared with one degree of freedom (3.84 at 5 %)."""
+        from iv_interpolation_amd.engine import age_weights, hsim_settings, weighted_settings
+        from iv_interpolation_amd.snapshots import weighted_var_frame
+        if min_returns is None:
+            min_returns = min(20, vol_span) if isinstance(vol_span, int) and vol_span > 0 else 20
+        try:
+            weighted_settings(window, lag, levels, min_scenarios, vol_span, min_returns, scale_cap)
+            age_weights(1, decay)
+            age_weights(1, vol_decay)
+            levels = hsim_settings(lag, window, levels, min_scenarios)[2]
+        except (ValueError, TypeError) as e:
+            return {"success": False, "error": str(e)}
+        rows, tables = [0], {}
+        eligible, exceed = [0] * len(levels), [0] * len(levels)
+
+        def weigh(builder, res, held, fit, reports):
+            rep = builder.var_weighted([res], reports, decay=decay, vol_span=vol_span, vol_decay=vol_decay, min_returns=min_returns, scale_cap=scale_cap)
+            table = weighted_var_frame(rep, [res])
+            self.store.write_table(VAR_W_TABLE, res.underlying, table)
+            rows[0] += len(table)
+            tables[res.underlying] = table
+            print(f"  {res.underlying}: {len(table)} weighted rows, decay {decay:g}, vol span {vol_span}")
+
+        def score(res, both):                                # run_var's eligibility and exceedance rule on varw
+            names = [f"varw_{tp:g}" for tp in levels]
+            mine = both[["date", "actual"]].merge(tables[res.underlying][["date"] + names], on="date", how="inner")
+            actual = mine["actual"].to_numpy(np.float64)
+            for n, name in enumerate(names):
+                var = mine[name].to_numpy(np.float64)
+                ok = np.isfinite(var) & np.isfinite(actual)
+                eligible[n] += int(ok.sum())
+                exceed[n] += int((ok & (actual < -var)).sum())
+        result = self._var_stage(book_file, lag, window, levels, min_scenarios, each=weigh, scored=score)
+        if "error" in result:
+            return result
+        backtest_w = [{"tp": tp, "eligible": e, "exceedances": x, "exceedance_rate": x / e if e else float("nan")}
+                      for tp, e, x in zip(levels, eligible, exceed)]
+        kupiec = [{"tp": b["tp"], "plain": kupiec_lr(b["eligible"], b["exceedances"], b["tp"]), "weighted": kupiec_lr(w["eligible"], w["exceedances"], w["tp"])}
+                  for b, w in zip(result["backtest"], backtest_w)]
+        print(f"WEIGHTED VAR COMPLETE: {rows[0]:,} rows; back-test: "
+              + ", ".join(f"tp {w['tp']:g}: {w['exceedances']}/{w['eligible']} ({w['exceedance_rate']:.3%}), Kupiec LR plain {k['plain']:.2f} / weighted {k['weighted']:.2f}"
+                          for w, k in zip(backtest_w, kupiec)))
+        return {**result, "success": result["success"] and rows[0] > 0, "w_rows": rows[0], "backtest_w": backtest_w, "kupiec": kupiec}
+
     def run_distribution(self) -> dict:
         """Risk-neutral distribution: the snapshots of run_surfaces and the slices of run_svi, then the
         quantiles, level probabilities and tails of every tenor row on the device, and one `iv_distribution` table per
@@ -901,6 +957,19 @@ class CompleteOptimizedPipeline:
         pass
 
 
+def kupiec_lr(n: int, x: int, tp: float) -> float:
+    """Kupiec's proportion-of-failures likelihood ratio of x exceedances among n eligible snapshots at the tail probability tp:
+    -2 [(n - x) ln(1 - tp) + x ln tp - (n - x) ln(1 - x / n) - x ln(x / n)], with 0 ln 0 = 0; NaN without an eligible snapshot.
+    Under a correct VaR it is chi-squared with one degree of freedom."""
+    import math
+    if n <= 0:
+        return float("nan")
+
+    def xlogy(a, b):
+        return a * math.log(b) if a > 0 else 0.0
+    return -2.0 * (xlogy(n - x, 1.0 - tp) + xlogy(x, tp) - xlogy(n - x, 1.0 - x / n) - xlogy(x, x / n))
+
+
 def _host_flags(a):
     import numpy as np
     return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
@@ -908,7 +977,7 @@ def _host_flags(a):
 
 def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed=None, surface_backend=None, implied_backend=None):
     parser = argparse.ArgumentParser(description="Complete Optimized Pipeline (MI355X engine)")
-    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "hedge", "whatif", "varci", "all"], default="all")
+    parser.add_argument("--task", choices=["interpolation", "implied", "bridge", "candles", "surfaces", "smiles", "arbitrage", "volindex", "svi", "distribution", "calendar", "ssvi", "risk", "explain", "var", "varattrib", "hedge", "whatif", "varci", "varw", "all"], default="all")
     parser.add_argument("--book", metavar="FILE", help="--task risk / explain / var: a CSV of symbol, quantity (default: every listed contract, +1 each)")
     parser.add_argument("--lag", type=int, default=1, metavar="N", help="--task explain / var: the pair is snapshot p and snapshot p + N (default 1)")
     parser.add_argument("--window", type=int, default=256, metavar="W", help="--task var: scenarios kept per snapshot (default 256)")
@@ -924,6 +993,10 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
     parser.add_argument("--block", type=int, default=None, metavar="L", help="--task varci: scenarios per block of the circular block bootstrap (default: the lag)")
     parser.add_argument("--seed", type=int, default=0, metavar="S", help="--task varci: the seed of the resampling (default 0)")
     parser.add_argument("--ci", default="0.05,0.95", metavar="P,P", help="--task varci: the probabilities of the interval's ends (default 0.05,0.95)")
+    parser.add_argument("--decay", type=float, default=0.99, metavar="D", help="--task varw: the weight of a scenario of age s is D^s, D in (0, 1] (default 0.99)")
+    parser.add_argument("--vol-span", type=int, default=0, metavar="M", help="--task varw: returns per running vol of the spot, 0..1024; 0 = no volatility scaling (default 0)")
+    parser.add_argument("--vol-decay", type=float, default=0.94, metavar="D", help="--task varw: the decay of the running vol's weights (default 0.94)")
+    parser.add_argument("--scale-cap", type=float, default=3.0, metavar="C", help="--task varw: the scaling factor is held inside [1/C, C] (default 3)")
     parser.add_argument("--group-by", choices=["expiry", "side"], default="expiry", help="--task varattrib: the groups the VaR is attributed to (default expiry)")
     parser.add_argument("--test", action="store_true", help="Test mode with 3 symbols")
     parser.add_argument("--symbols", type=int, help="Limit number of symbols")
@@ -996,6 +1069,9 @@ def main(argv=None, backend=None, bridge_backend=None, candle_backend=None, seed
             elif args.task == "varci":
                 result = pipeline.run_varci(args.book, args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios,
                                             args.replicates, args.block, args.seed, [float(x) for x in args.ci.split(",") if x.strip()])
+            elif args.task == "varw":
+                result = pipeline.run_varw(args.book, args.lag, args.window, [float(x) for x in args.levels.split(",") if x.strip()], args.min_scenarios,
+                                           args.decay, args.vol_span, args.vol_decay, args.scale_cap)
             else:
                 result = pipeline.run_task2_candle_reconstruction(symbols)
         return 0 if result["success"] else 1

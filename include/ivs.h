@@ -1100,6 +1100,70 @@ size_t ivs_hsim_bootstrap_workspace_bytes(int64_t B, int32_t n_rep, int32_t nL);
 int ivs_hsim_bootstrap_f64(const ivs_bootstrap_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Age-weighted, volatility-scaled historical-simulation VaR and expected shortfall (rules W0-W9; additive to
+ * ABI 5).  The call works on rows: pnl and scen_flags [B][window] as an ivs_svi_hsim_f64 call wrote them (INPUTS), with the lag of
+ * that call, and on the snapshots' spot [B] when scaling is on (vol_span = M > 0).  Scenario s of a row has the weight weight[s] (by
+ * its age; NULL: every weight 1.0).  With M > 0 a running vol of the spot is formed first: r_j = spot[j] / spot[j-1] - 1.0 (valid iff
+ * both spots are finite and > 0 and r_j is finite), sigma[j] = sqrt(sum_k a_k (r_{j-k} r_{j-k}) / sum_k a_k) over k = 0..M-1 in
+ * ascending k from +0.0, a_k = vol_weight[k], terms with j - k < 1 or an invalid return left out of both sums; NaN with fewer than
+ * min_returns terms, with an a_k among them that is not finite and >= 0, or with a quotient that is not finite and > 0.  Scenario s of
+ * snapshot p starts at j = p - lag - s; it is multiplied by f = min(max(sigma[p] / sigma[j], 1 / scale_cap), scale_cap): z = pnl f.
+ * With M == 0 z is pnl to the bit and neither sigma nor spot is read.
+ *   flags_w [B][window] (int32)        scen_flags | IVS_HW_NO_VOL (M > 0 and j < 0, or either sigma not finite and > 0) |
+ *                                      IVS_HW_BAD_WEIGHT (weight[s] not finite and >= 0).  Required.
+ *   n_valid_w, worst_w [B] (int32)     the ranked scenarios (flags_w == 0 and z a number), and the s of the smallest z (ties to the
+ *                                      lower s, -0.0 == +0.0; -1 without one).  Required.
+ *   wsum, n_eff [B]                    W = the sum of the ranked scenarios' weights, in the order of rule B5 over s (passes of 256), and
+ *                                      (W W) / W2 with W2 the sum of the rounded squares in that order (NaN when W2 is not > 0).  Required.
+ *   var_w, es_w [B][nL]                the weighted tail at every level: target = tp W; up the ranks in ascending z the weights are
+ *                                      added until the next one would reach the target; 0.0 - z at that rank, and 0.0 - (the sum of the
+ *                                      rounded w z below it + (target - the weight below it) z at it) / target: the exact tail mean,
+ *                                      with a fractional share of the boundary scenario.  NaN unless n >= min_scen, n > 0 and W is
+ *                                      finite and > 0.
+ *   pnl_w, scale [B][window]           z (NaN where the scenario is not ranked) and f (NaN where none was formed, 1.0 with M == 0).
+ *                                      Either may be NULL.  pnl_w with flags_w is a row in ivs_svi_hsim_f64's sense.
+ *   sigma [B]                          output at stages 0 and 1, INPUT at stages 2; required iff M > 0.
+ * stages: 0 = both launches, 1 = sigma alone, 2 = the tail alone on sigma as given.  With M == 0, stages 1 has nothing to do.
+ * The bits of a row's outputs depend on the row, the sigmas it reads, weight, tail_probs, min_scen and the settings alone.
+ *
+ * No workspace (NULL, 0).  IVS_EINVAL: null args, a negative size (B, nL), a null required pointer (tail_probs with nL > 0; at
+ * stages 0 and 2 pnl, scen_flags, flags_w, n_valid_w, worst_w, wsum, n_eff, and with nL > 0 var_w, es_w; with M > 0 sigma, and at
+ * stages 0 and 1 also spot and vol_weight).  IVS_ERANGE: lag < 1, window outside 1..1024, nL > 8, a tail probability outside (0, 1),
+ * min_scen < 1, vol_span outside 0..1024, with M > 0 min_returns outside 1..M or scale_cap not finite or < 1, stages outside 0..2,
+ * B*window >= 2^31.  The limits are checked before the zero-size return; B == 0 is a no-op.  A refused call launches nothing and
+ * touches no buffer.  No allocation, no synchronisation (capturable), no dynamic LDS; at most two launches, one when M == 0 or
+ * stages != 0.
+ */
+enum {
+    IVS_HW_NO_VOL = 8,
+    IVS_HW_BAD_WEIGHT = 16
+};
+typedef struct ivs_hsim_weighted_args {
+    const double* pnl;         /* [B][window], input */
+    const int32_t* scen_flags; /* [B][window], input */
+    int64_t B;
+    int32_t window;            /* 1..1024 */
+    int32_t lag;               /* >= 1 */
+    int32_t nL;                /* 0..8 */
+    int32_t min_scen;          /* >= 1 */
+    const double* tail_probs;  /* host */
+    const double* weight;      /* [window] by age, may be NULL: 1.0 */
+    const double* spot;        /* [B], with vol_span > 0 */
+    const double* vol_weight;  /* [vol_span], with vol_span > 0 */
+    int32_t vol_span;          /* 0..1024; 0 = no scaling */
+    int32_t min_returns;       /* 1..vol_span */
+    double scale_cap;          /* finite, >= 1 */
+    int32_t stages;            /* 0..2 */
+    double* sigma;             /* [B], with vol_span > 0 */
+    double* var_w; double* es_w; /* [B][nL] */
+    int32_t* n_valid_w; int32_t* worst_w; /* [B] */
+    double* wsum; double* n_eff; /* [B] */
+    double* pnl_w; double* scale; /* [B][window], may be NULL */
+    int32_t* flags_w;          /* [B][window] */
+} ivs_hsim_weighted_args;
+int ivs_hsim_weighted_f64(const ivs_hsim_weighted_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Black-Scholes Greeks epilogue (reference src/interpolation/greeks.py:12-43, BlackScholesGreeks.calculate_greeks):
  * elementwise over n options.  is_put [n] (1 = put) or NULL -> every option uses default_is_put.
  * theta is per day (/365), vega and rho per 1 % (/100), put rho without sign flip -- all as the reference.
@@ -1189,7 +1253,7 @@ int     ivs_bridge_candles_f64(const double* price, const double* volume, const 
  * ivs_surface_arbitrage_f64 / ivs_surface_moments_f64 / ivs_svi_slices_f64 / ivs_svi_distribution_f64 call on this thread
  * dispatched to (host string); ivs_svi_calendar_f64, ivs_svi_eval_f64, ivs_ssvi_surface_f64, ivs_bs_price_f64,
  * ivs_bs_implied_vol_f64, ivs_svi_greeks_f64, ivs_svi_book_f64, ivs_svi_explain_f64, ivs_svi_hsim_f64, ivs_svi_hsim_attrib_f64, ivs_svi_hedge_f64,
- * ivs_svi_whatif_f64 and ivs_hsim_bootstrap_f64 set it too */
+ * ivs_svi_whatif_f64, ivs_hsim_bootstrap_f64 and ivs_hsim_weighted_f64 set it too */
 const char* ivs_last_kernel(void);
 
 /*

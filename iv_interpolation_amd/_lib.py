@@ -42,6 +42,8 @@ HG_MAX_INST, HG_MAX_ROUNDS = 64, 8
 HG_CALL, HG_PUT, HG_UNDERLYING = 0, 1, 2                         # inst_kind
 WI_MAX_RUNGS = 16                                                # sizes per candidate of the what-if ladder
 BOOT_MAX_REP, BOOT_MAX_BLOCK, BOOT_MAX_CI = 1024, 1024, 8        # replicates, block length and interval probabilities of the bootstrap
+HW_NO_VOL, HW_BAD_WEIGHT = 8, 16                                 # IVS_HW_*: the bits the weighted tail adds to IVS_HS_*
+HW_MAX_SPAN = 1024                                               # returns per running vol of the spot
 # IVS_SS_*: per-row flags of the SSVI surface; IVS_SF_*: its per-snapshot flags
 SS_RAISED, SS_HOLES, SS_DEAD, SS_BUTTERFLY = 1, 4, 8, 16
 SF_EDGE_RHO, SF_EDGE_GAMMA, SF_EDGE_ETA_LOW, SF_SURF_DEAD, SF_AT_BOUND, SF_UNORDERED = 1, 2, 4, 8, 16, 32
@@ -253,6 +255,15 @@ class BootstrapArgs(C.Structure):
                 ("var0", _p), ("es0", _p), ("n_scen", _p), ("mean", _p), ("variance", _p), ("quant", _p), ("rep", _p)]
 
 
+class WeightedArgs(C.Structure):
+    """ivs_hsim_weighted_args of include/ivs.h (field for field)."""
+    _fields_ = [("pnl", _p), ("scen_flags", _p), ("B", _i64), ("window", _i32), ("lag", _i32), ("nL", _i32), ("min_scen", _i32),
+                ("tail_probs", C.POINTER(C.c_double)), ("weight", _p), ("spot", _p), ("vol_weight", _p),
+                ("vol_span", _i32), ("min_returns", _i32), ("scale_cap", C.c_double), ("stages", _i32),
+                ("sigma", _p), ("var_w", _p), ("es_w", _p), ("n_valid_w", _p), ("worst_w", _p), ("wsum", _p), ("n_eff", _p),
+                ("pnl_w", _p), ("scale", _p), ("flags_w", _p)]
+
+
 class SsviArgs(C.Structure):
     """ivs_ssvi_args of include/ivs.h (field for field)."""
     _fields_ = [("vol", _p), ("Kq", _p), ("kq_stride", _i64), ("Tq", _p), ("tq_stride", _i64),
@@ -308,6 +319,7 @@ SIGNATURES = {
     "ivs_svi_whatif_f64": (C.c_int, [C.POINTER(WhatIfArgs), _p, _sz, _p]),
     "ivs_hsim_bootstrap_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ivs_hsim_bootstrap_f64": (C.c_int, [C.POINTER(BootstrapArgs), _p, _sz, _p]),
+    "ivs_hsim_weighted_f64": (C.c_int, [C.POINTER(WeightedArgs), _p, _sz, _p]),
     "ivs_ssvi_surface_f64": (C.c_int, [C.POINTER(SsviArgs), _p, _sz, _p]),
     "ivs_surface_batch_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _i32,
                                         _p, _p, _i32, _i32, _p, _sz, _p]),

@@ -18,6 +18,7 @@
 #include "ivs_host.hpp"
 #include "ivs_hsim.hpp"
 #include "ivs_hsim_attrib.hpp"
+#include "ivs_hsim_weighted.hpp"
 #include "ivs_implied.hpp"
 #include "ivs_moments.hpp"
 #include "ivs_risk.hpp"
@@ -659,6 +660,56 @@ int ivs_hsim_bootstrap_f64(const ivs_bootstrap_args* a, void* workspace, size_t 
     p.rep = a->rep ? a->rep : static_cast<double*>(workspace);          // C9: the one way through global memory
     hipLaunchKernelGGL(ivs::hsim_bootstrap_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, static_cast<hipStream_t>(stream), p);
     return end_call("hsim_bootstrap_kernel");
+}
+
+int ivs_hsim_weighted_f64(const ivs_hsim_weighted_args* a, void*, size_t, void* stream) {
+    const char* fn = "ivs_hsim_weighted_f64";
+    if (int rc = begin_call(fn, a)) return rc;
+    if (a->B < 0 || a->nL < 0) return fail(IVS_EINVAL, "%s: negative size", fn);
+    if (a->lag < 1) return fail(IVS_ERANGE, "%s: lag=%d < 1", fn, a->lag);
+    if (a->window < 1 || a->window > ivs::HS_MAX_WINDOW)
+        return fail(IVS_ERANGE, "%s: window=%d outside [1,%d]", fn, a->window, ivs::HS_MAX_WINDOW);
+    if (a->nL > ivs::HS_MAX_LEVELS) return fail(IVS_ERANGE, "%s: nL=%d > %d tail probabilities", fn, a->nL, ivs::HS_MAX_LEVELS);
+    if (a->nL > 0 && !a->tail_probs) return fail(IVS_EINVAL, "%s: null tail probabilities", fn);
+    for (int l = 0; l < a->nL; ++l)
+        if (!(a->tail_probs[l] > 0.0 && a->tail_probs[l] < 1.0))
+            return fail(IVS_ERANGE, "%s: tail probability %d (%g) is not inside (0, 1)", fn, l, a->tail_probs[l]);
+    if (a->min_scen < 1) return fail(IVS_ERANGE, "%s: min_scen=%d < 1", fn, a->min_scen);
+    const int M = a->vol_span;
+    if (M < 0 || M > ivs::HW_MAX_SPAN) return fail(IVS_ERANGE, "%s: vol_span=%d outside [0,%d]", fn, M, ivs::HW_MAX_SPAN);
+    if (M > 0 && (a->min_returns < 1 || a->min_returns > M))
+        return fail(IVS_ERANGE, "%s: min_returns=%d outside [1,%d]", fn, a->min_returns, M);
+    if (M > 0 && !(a->scale_cap >= 1.0 && a->scale_cap < __builtin_inf()))
+        return fail(IVS_ERANGE, "%s: scale_cap=%g is not finite and >= 1", fn, a->scale_cap);
+    if (a->stages < 0 || a->stages > 2) return fail(IVS_ERANGE, "%s: stages=%d outside [0,2]", fn, a->stages);
+    if (a->B > 0x7fffffffLL / a->window)
+        return fail(IVS_ERANGE, "%s: %lld rows x %d scenarios exceed one launch", fn, (long long)a->B, a->window);
+    if (a->B == 0) return IVS_OK;                                                                  // W9
+    const bool ewma = M > 0 && a->stages != 2, tail = a->stages != 1;
+    if ((M > 0 && !a->sigma) || (ewma && (!a->spot || !a->vol_weight)) ||
+        (tail && (!a->pnl || !a->scen_flags || !a->flags_w || !a->n_valid_w || !a->worst_w || !a->wsum || !a->n_eff ||
+                  (a->nL > 0 && (!a->var_w || !a->es_w)))))
+        return fail(IVS_EINVAL, "%s: null pointer", fn);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (ewma) {
+        ivs::SpotEwmaParams e{};
+        e.spot = a->spot; e.vol_weight = a->vol_weight; e.B = a->B; e.M = M; e.min_returns = a->min_returns; e.sigma = a->sigma;
+        const int64_t grid = (a->B + ivs::RK_BLOCK - 1) / ivs::RK_BLOCK;
+        hipLaunchKernelGGL(ivs::spot_ewma_kernel, dim3((unsigned)grid), dim3(ivs::RK_BLOCK), 0, st, e);
+        if (int rc = end_call("spot_ewma_kernel")) return rc;
+    }
+    if (tail) {
+        ivs::WTailParams t{};
+        t.pnl = a->pnl; t.scen_flags = a->scen_flags; t.weight = a->weight; t.sigma = M > 0 ? a->sigma : nullptr;
+        t.window = a->window; t.nL = a->nL; t.min_scen = a->min_scen; t.lag = a->lag;
+        t.cap = M > 0 ? a->scale_cap : 1.0; t.cap_lo = 1.0 / t.cap;     // W0: formed once, here
+        for (int l = 0; l < a->nL; ++l) t.tp[l] = a->tail_probs[l];
+        t.var_w = a->var_w; t.es_w = a->es_w; t.n_valid_w = a->n_valid_w; t.worst_w = a->worst_w; t.wsum = a->wsum; t.n_eff = a->n_eff;
+        t.pnl_w = a->pnl_w; t.scale = a->scale; t.flags_w = a->flags_w;
+        hipLaunchKernelGGL(ivs::hsim_wtail_kernel, dim3((unsigned)a->B), dim3(ivs::RK_BLOCK), 0, st, t);
+        return end_call("hsim_wtail_kernel");
+    }
+    return IVS_OK;
 }
 
 int ivs_ssvi_surface_f64(const ivs_ssvi_args* a, void*, size_t, void* stream) {

@@ -1116,6 +1116,113 @@ def hsim_bootstrap(pnl, scen_flags, tail_probs=DEFAULT_TAIL_PROBS, min_scen: int
     return {**{k: out[k] for k in shapes}, "se": se}
 
 
+WEIGHTED_OUTPUTS = ("var_w", "es_w", "n_valid_w", "worst_w", "wsum", "n_eff", "pnl_w", "scale", "flags_w", "sigma")
+WEIGHTED_OPTIONAL = ("pnl_w", "scale")
+
+
+def age_weights(window, decay):
+    """The weights of an age-weighted historical simulation as a host float64 array [window]: w_0 = 1.0 and
+    w_{s+1} = w_s x decay by repeated multiplication, for a decay in (0, 1].  The same call gives the a_k of the running vol."""
+    import math
+    import numpy as np
+    if int(window) != window or window < 1:
+        raise ValueError(f"window {window!r} is not an integer >= 1")
+    decay = float(decay)
+    if not (math.isfinite(decay) and 0.0 < decay <= 1.0):
+        raise ValueError(f"decay {decay!r} is not inside (0, 1]")
+    w = np.empty(int(window), np.float64)
+    x = np.float64(1.0)
+    for s in range(int(window)):
+        w[s] = x
+        x = x * np.float64(decay)
+    return w
+
+
+def weighted_settings(window, lag, tail_probs, min_scen, vol_span=0, min_returns=20, scale_cap=3.0, stages=0):
+    """The host-side checks of a weighted historical simulation: lag, window, tail_probs and min_scen as
+    hsim_settings has them, vol_span an integer in 0..1024, and with vol_span > 0 min_returns an integer in 1..vol_span and scale_cap
+    finite and >= 1; stages 0, 1 or 2; ValueError otherwise.  Returns (window, lag, tail_probs as a list, min_scen, vol_span,
+    min_returns, scale_cap, stages)."""
+    import math
+    lag, window, tp, min_scen, _ = hsim_settings(lag, window, tail_probs, min_scen)
+    if int(vol_span) != vol_span or not 0 <= vol_span <= _lib.HW_MAX_SPAN:
+        raise ValueError(f"vol_span {vol_span!r} is not an integer in 0..{_lib.HW_MAX_SPAN}")
+    if int(min_returns) != min_returns:
+        raise ValueError(f"min_returns {min_returns!r} is not an integer")
+    scale_cap = float(scale_cap)
+    if vol_span > 0:
+        if not 1 <= min_returns <= vol_span:
+            raise ValueError(f"min_returns {min_returns!r} is not an integer in 1..{vol_span}, the vol_span")
+        if not (math.isfinite(scale_cap) and scale_cap >= 1.0):
+            raise ValueError(f"scale_cap {scale_cap!r} is not finite and >= 1")
+    if stages not in (0, 1, 2):
+        raise ValueError(f"stages {stages!r} is not 0, 1 or 2")
+    return window, lag, tp, min_scen, int(vol_span), int(min_returns), scale_cap, int(stages)
+
+
+def hsim_weighted(pnl, scen_flags, spot=None, *, lag: int = 1, tail_probs=DEFAULT_TAIL_PROBS, min_scen: int = 20, weight=None,
+                  vol_span: int = 0, vol_weight=None, min_returns: int = 20, scale_cap: float = 3.0, stages: int = 0, sigma=None,
+                  want=WEIGHTED_OPTIONAL, out=None, stream=None):
+    """Age-weighted, volatility-scaled VaR and expected shortfall of rows of scenario P&Ls (ivs_hsim_weighted_f64; rules W0-W9 of
+    DESIGN.md section 24).  pnl float64 and scen_flags int32 [B, window] as svi_hsim returns them, with that call's lag.  weight
+    float64 [window] on the device: the probability weight of a scenario by its age s (None: 1.0 each; age_weights makes the usual
+    ones).  vol_span = M > 0 turns the scaling on: spot float64 [B] of the snapshots and vol_weight float64 [M] on the device give the
+    running vol sigma [B]; scenario s of snapshot p is multiplied by sigma[p] / sigma[p - lag - s], held inside [1 / scale_cap,
+    scale_cap].  weighted_settings has the limits.  stages: 0 = everything, 1 = sigma alone (every other output None), 2 = the tail
+    alone on `sigma` as given (float64 [B]; also accepted as out["sigma"]).
+    want: which of pnl_w and scale to return (None otherwise).  `out`: optional dict of preallocated outputs.
+    Returns dict(var_w, es_w [B,nL]; n_valid_w, worst_w int32 [B]; wsum, n_eff [B]; pnl_w, scale [B,window]; flags_w int32 [B,window]:
+    scen_flags with the _lib.HW_* bits; sigma [B], None with vol_span == 0) of device tensors."""
+    torch = require_device()
+    want = _wanted(want, WEIGHTED_OPTIONAL)
+    pnl = _f64(torch, pnl, "pnl")
+    if not scen_flags.is_cuda or scen_flags.dtype != torch.int32:
+        raise TypeError("scen_flags must be a CUDA int32 tensor")
+    scen_flags = scen_flags.contiguous()
+    if pnl.dim() != 2 or tuple(scen_flags.shape) != tuple(pnl.shape):
+        raise ValueError("pnl and scen_flags must be [B, window], of one shape")
+    B, window = pnl.shape
+    window, lag, tp, min_scen, M, min_returns, scale_cap, stages = weighted_settings(window, lag, tail_probs, min_scen, vol_span, min_returns,
+                                                                                      scale_cap, stages)
+    nL = len(tp)
+    if B * window >= 2 ** 31:
+        raise ValueError(f"{B} rows x {window} scenarios exceed one launch")
+    if weight is not None:
+        weight = _f64(torch, weight, "weight")
+        if tuple(weight.shape) != (window,):
+            raise ValueError(f"weight must be [window] = [{window}]")
+    if M > 0 and stages != 2:
+        if spot is None or vol_weight is None:
+            raise ValueError("vol_span > 0 needs spot and vol_weight")
+        spot, vol_weight = _f64(torch, spot, "spot"), _f64(torch, vol_weight, "vol_weight")
+        if spot.numel() != B or tuple(vol_weight.shape) != (M,):
+            raise ValueError(f"spot must hold one price per row and vol_weight must be [vol_span] = [{M}]")
+    else:
+        spot = vol_weight = None
+    out = dict(out or {})
+    if sigma is not None:
+        if "sigma" in out and out["sigma"] is not sigma:
+            raise ValueError("sigma was given twice: as an argument and in out")
+        out["sigma"] = sigma
+    if M > 0 and stages == 2 and out.get("sigma") is None:
+        raise ValueError("stages 2 with vol_span > 0 reads sigma: it must be given")
+    tail = stages != 1
+    i32, f64 = torch.int32, torch.float64
+    shapes = {"var_w": ((B, nL), f64, tail), "es_w": ((B, nL), f64, tail), "n_valid_w": ((B,), i32, tail), "worst_w": ((B,), i32, tail),
+              "wsum": ((B,), f64, tail), "n_eff": ((B,), f64, tail), "pnl_w": ((B, window), f64, tail and "pnl_w" in want),
+              "scale": ((B, window), f64, tail and "scale" in want), "flags_w": ((B, window), i32, tail), "sigma": ((B,), f64, M > 0)}
+    out = _outputs(torch, out, shapes, pnl.device)
+    a = _lib.WeightedArgs()
+    a.pnl, a.scen_flags, a.B, a.window, a.lag = _ptr(pnl), _ptr(scen_flags), B, window, lag
+    a.tail_probs, a.nL, a.min_scen = _doubles(tp), nL, min_scen
+    a.weight, a.spot, a.vol_weight = _ptr(weight), _ptr(spot), _ptr(vol_weight)
+    a.vol_span, a.min_returns, a.scale_cap, a.stages = M, min_returns, scale_cap, stages
+    for k in shapes:
+        setattr(a, k, _ptr(out[k]))
+    _call(torch, "ivs_hsim_weighted_f64", a, stream, pnl, scen_flags, weight, spot, vol_weight, *out.values())
+    return {k: out[k] for k in shapes}
+
+
 def place_output(run, shape, tries: int = 8, dtype=None, warm: int = 8, timed: int = 3):
     """Pick the output buffer a persistent caller should keep.  On MI355X the same surface kernel on the same inputs runs up
     to 8 % faster or slower depending on WHICH allocation it writes to (stable per buffer, independent of offsets inside

@@ -400,6 +400,36 @@ class BootstrapReport:
     n_valid: object                  # [B] int32
 
 
+@dataclass
+class WeightedVarReport:
+    """One underlying's age-weighted, volatility-scaled VaR and expected shortfall beside those of a VarReport (rules W0-W9).  The
+    value arrays are device tensors with the HIP backend (host arrays with an injected CPU backend)."""
+    underlying: str
+    dates: pd.DatetimeIndex          # [B]
+    lag: int
+    window: int
+    tail_probs: np.ndarray           # [nL]
+    min_scenarios: int
+    decay: float                     # the weight of a scenario of age s is decay^s
+    vol_span: int                    # returns per running vol; 0 = no scaling
+    vol_decay: float
+    min_returns: int
+    scale_cap: float
+    var_w: object                    # [B, nL] losses are positive
+    es_w: object                     # [B, nL]
+    n_valid_w: object                # [B] int32
+    worst_w: object                  # [B] int32
+    wsum: object                     # [B] the mass of the ranked scenarios
+    n_eff: object                    # [B] its square over the sum of squares: the effective number of scenarios
+    pnl_w: object                    # [B, window] the scaled scenario P&Ls, NaN where not ranked
+    scale: object                    # [B, window] the factor of every scenario
+    flags_w: object                  # [B, window] int32, IVS_HS_* | IVS_HW_*
+    sigma: object                    # [B] the running vol of the spot; None without scaling
+    var: object                      # [B, nL] the VarReport's
+    es: object                       # [B, nL]
+    n_valid: object                  # [B] int32
+
+
 class HipBackend:
     """Uploads one underlying's packed arrays and runs the snapshot kernel, then the surface kernels, on the current
     HIP device.  Results stay on the device."""
@@ -501,6 +531,12 @@ class HipBackend:
     def bootstrap(self, pnl, scen_flags, tail_probs, min_scen, n_rep, block, seed, ci_probs, want_rep=False):
         return engine.hsim_bootstrap(pnl, scen_flags, tail_probs, min_scen, n_rep, block, seed, ci_probs, want_rep=want_rep,
                                      stream=self.stream)
+
+    def weighted(self, pnl, scen_flags, spot, lag, tail_probs, min_scen, weight, vol_span, vol_weight, min_returns, scale_cap):
+        d = lambda a: None if a is None else self._up(a, np.float64)  # noqa: E731
+        return engine.hsim_weighted(pnl, scen_flags, spot if vol_span > 0 else None, lag=lag, tail_probs=tail_probs, min_scen=min_scen,
+                                    weight=d(weight), vol_span=vol_span, vol_weight=d(vol_weight), min_returns=min_returns,
+                                    scale_cap=scale_cap, stream=self.stream)
 
 
 def _host(a):
@@ -1055,6 +1091,28 @@ class SnapshotSurfaceBuilder:
             reports.append(BootstrapReport(h.underlying, h.dates, np.asarray(tp, np.float64), min_scen, R, L, sd, np.asarray(cis, np.float64),
                                            q["var0"], q["es0"], q["n_scen"], q["mean"], q["variance"], q["se"], q["quant"], h.var, h.es,
                                            h.n_valid))
+        return reports
+
+    # ------------------------------------------------------------------ weighted, scaled VaR
+    def var_weighted(self, results: Sequence[SnapshotSurfaces], var_reports: Sequence["VarReport"], decay: float = 0.99, vol_span: int = 0,
+                     vol_decay: float = 0.94, min_returns: int = 20, scale_cap: float = 3.0) -> List["WeightedVarReport"]:
+        """The VaR and expected shortfall of var() with a probability per scenario that decays with its age, decay^s, and, with
+        vol_span > 0, every scenario scaled by today's running vol of the spot over the vol at the scenario's start (rules W0-W9):
+        one WeightedVarReport per VarReport.  The running vol is the root of the vol_decay^k-weighted mean of the last vol_span
+        squared returns of the snapshots' spot (NaN before min_returns of them); the factor is held inside [1 / scale_cap,
+        scale_cap].  The spot comes from `results`, the rows are the reports' own: nothing is revalued."""
+        from .engine import age_weights, weighted_settings
+        be = self._backend or HipBackend()
+        reports = []
+        for r, h in zip(results, var_reports):
+            window, lag, tp, min_scen, M, mr, cap, _ = weighted_settings(h.window, h.lag, h.tail_probs, h.min_scenarios, vol_span, min_returns,
+                                                                         scale_cap)
+            weight = age_weights(window, decay)
+            vol_weight = age_weights(M, vol_decay) if M > 0 else None
+            q = be.weighted(h.pnl, h.scen_flags, r.spot, lag, tp, min_scen, weight, M, vol_weight, mr, cap)
+            reports.append(WeightedVarReport(h.underlying, h.dates, lag, window, np.asarray(tp, np.float64), min_scen, float(decay), M,
+                                             float(vol_decay), mr, cap, q["var_w"], q["es_w"], q["n_valid_w"], q["worst_w"], q["wsum"],
+                                             q["n_eff"], q["pnl_w"], q["scale"], q["flags_w"], q["sigma"], h.var, h.es, h.n_valid))
         return reports
 
     # ------------------------------------------------------------------ output
@@ -1619,6 +1677,28 @@ def confidence_frame(reports: Sequence[BootstrapReport], snapshots: Sequence[Sna
         parts.append(pd.DataFrame(cols))
     if not parts:
         return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "n_valid": pd.Series(dtype=np.int32)})
+    df = pd.concat(parts, ignore_index=True)
+    return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
+
+
+def weighted_var_frame(reports: Sequence[WeightedVarReport], snapshots: Sequence[SnapshotSurfaces]) -> pd.DataFrame:
+    """One row per snapshot with quotes > 0, ordered by (underlying, date): columns underlying, date, n_valid (the scenarios the
+    weighted tail ranks), n_eff, sigma (NaN without scaling) and per tail probability var_<tp>, es_<tp> (the VarReport's) beside
+    varw_<tp>, esw_<tp> (the weighted, scaled ones; losses are positive)."""
+    parts = []
+    for p, r in zip(reports, snapshots):
+        keep = np.flatnonzero(_host(r.quotes) > 0)
+        cols = {"underlying": p.underlying, "date": p.dates[keep], "n_valid": _host(p.n_valid_w)[keep].astype(np.int32),
+                "n_eff": _host(p.n_eff)[keep], "sigma": np.full(len(keep), np.nan) if p.sigma is None else _host(p.sigma)[keep]}
+        var, es, var_w, es_w = _host(p.var)[keep], _host(p.es)[keep], _host(p.var_w)[keep], _host(p.es_w)[keep]
+        for n, tp in enumerate(p.tail_probs):
+            for name, a in (("var", var), ("es", es), ("varw", var_w), ("esw", es_w)):
+                cols[f"{name}_{float(tp):g}"] = a[:, n]
+        parts.append(pd.DataFrame(cols))
+    if not parts:
+        f64 = pd.Series(dtype=np.float64)
+        return pd.DataFrame({"underlying": pd.Series(dtype=object), "date": pd.Series(dtype="datetime64[ns]"), "n_valid": pd.Series(dtype=np.int32),
+                             "n_eff": f64, "sigma": f64})
     df = pd.concat(parts, ignore_index=True)
     return df.sort_values(["underlying", "date"], kind="stable").reset_index(drop=True)
 
